@@ -8,12 +8,16 @@ operands, fp32 accumulation), then the cosine distance of the step's embeddings 
 (12 180 x 4096, row-sharded over the ranks). One "step" = forward + [RCCL all-gather of embeddings, N > 1] +
 distance matrix against the rank's gallery shard. Inputs are resident in HBM before the timed region.
 
-    python bench.py                              # 1 GPU, 20 steps
+    python bench.py                              # 1 GPU, 20 steps: the headline figure only
+    python bench.py --full                       # the same, plus every secondary measurement and check listed below
+    python bench.py --dump-outputs DIR           # also write the last timed step's outputs to DIR/*.npy (float32)
     python bench.py --gpus 8 --steps 20          # starts 8 ranks itself (fresh child processes, one per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W   # the driver's form: every process is one rank
 
-Rank 0 prints ONE JSON line: value = whole-job frames/s (all ranks) over EXACTLY --steps steps, plus
+Rank 0 prints ONE JSON line: value = whole-job frames/s (all ranks) over EXACTLY --steps steps, ms_per_step = milliseconds
+per timed step. A plain run sets up, warms up, times the steps, writes --dump-outputs and prints that line. With --full
+the line also carries (each --no-* option drops one part)
   sustained_value : the same step repeated for >= 2 s (the chip runs at its power limit; a 74 ms burst flatters it)
   roofline        : the dominant kernel (conv1x1_duo_kernel / conv1x1_duo_persist_kernel: every 1x1 GEMM of layer 4 and the two-source
                     first blocks of layers 2 / 3; bound to this kernel in every run): algorithmic flops per launch / average launch
@@ -83,7 +87,35 @@ def parse(argv=None):
     ap.add_argument("--host-cores", type=int, default=0,
                     help="restrict this process to its first K allowed CPUs (os.sched_setaffinity at start-up, before any GPU call)")
     ap.add_argument("--host-issue-only", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every secondary measurement and check (extra blocks, host issue, sustained rate, "
+                         "per-kernel rooflines, precision modes, accuracy, config5, config4, CPU baseline; the --no-* options "
+                         "drop parts of it); without it the run prints the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned on rank 0 -- the distance matrix and the embeddings it was "
+                         "computed from -- as DIR/<name>.npy in float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32. When they hold more than DUMP_BUDGET_BYTES together, every array
+    keeps a fixed, seeded sample of its rows (the same rows from run to run for the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_BUDGET_BYTES / total))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -472,7 +504,8 @@ def other_lp16_child(args):
     other = "bf16" if args.precision == "fp16" else "fp16"
     cmd = [sys.executable, os.path.abspath(__file__), "--precision", other, "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--batch", str(args.batch), "--seq-len", str(args.seq_len), "--metric", args.metric, "--no-cpu-baseline", "--no-accuracy",
-           "--no-config5", "--no-config4", "--no-modes", "--sustain-seconds", "0", "--profile-steps", "0", "--embedding-error"]
+           "--no-config5", "--no-config4", "--no-modes", "--sustain-seconds", "0", "--profile-steps", "0", "--embedding-error",
+           "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("AGRL_HIP_LP16", "AGRL_HIP_LIB", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -735,8 +768,11 @@ def main():
             step_no[0] += 1
             return model(clip_sets[i], adj_sets[i])
 
+    last_emb = [None]
+
     def step(eager=False):
         emb = forward(eager)                          # (B, 4096) fp32
+        last_emb[0] = emb
         if match_stream is None:
             return match(emb)
         # N > 1: the exchange + match of this batch run on their own HIP stream, so the collective (and the skew
@@ -768,7 +804,7 @@ def main():
         os._exit(int(os.environ.get("AGRL_BENCH_FAULT_CODE", "3")))
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_dist = step()
     sync()
     elapsed_local = time.perf_counter() - t0
     elapsed = reduce_max(elapsed_local)
@@ -778,7 +814,45 @@ def main():
         allt = torch.empty((world,), dtype=torch.float64, device=device)
         dist.all_gather_into_tensor(allt, t)
         per_rank_ms = allt.tolist()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the distance matrix of the batch against this rank's
+        # gallery shard, and the embeddings it was computed from
+        dump_outputs(args.dump_outputs, {"distmat": last_dist, "embeddings": last_emb[0]})
 
+    frames = B * S * world * args.steps
+    backend = dist.get_backend() if multi else None
+    result = {
+        "metric": "frames/sec (fwd+GCN+distmat), MARS seq_len=8",
+        "value": round(frames / elapsed, 1),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.precision,
+        "data": "synthetic",
+        "config": {"workload": "MARS seq_len=8 bs=32/GPU %s fwd+distmat (BASELINE configs[1]): 256x128 frames, VMGN "
+                               "ResNet50x2-branch + 2 graph layers, %s distmat vs resident %d x 4096 gallery" %
+                               (args.precision, args.metric, GALLERY_ROWS),
+                   "global_batch": B * world, "seq_len": S, "frames_per_step": B * S * world,
+                   "gallery_rows_per_gpu": hi - lo, "parallelism": "dp%d" % world, "hip_graph": bool(args.graph),
+                   "ranks": world, "collective_backend": ("rccl" if backend == "nccl" else backend),
+                   "devices_visible": torch.cuda.device_count(), "library": os.path.basename(_hip.LIB_PATH),
+                   "per_rank_ms_per_step": [round(x, 3) for x in per_rank_ms],
+                   "clip_batches_rotated": NCLIPS, "clip_bytes_rotated": NCLIPS * B * S * 3 * 256 * 128 * 4},
+    }
+    if not args.full and not args.host_issue_only:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on
     # three more blocks of the same K steps (each bracketed like the first): the box-to-box and run-to-run spread of this chip
     # is larger than most kernel-level wins, so the line also carries the median block
     block_ms = []
@@ -828,30 +902,7 @@ def main():
         sus_elapsed = reduce_max(time.perf_counter() - t0)
         sustained = (n_sus, sus_elapsed)
 
-    frames = B * S * world * args.steps
-    backend = dist.get_backend() if multi else None
-    result = {
-        "metric": "frames/sec (fwd+GCN+distmat), MARS seq_len=8",
-        "value": round(frames / elapsed, 1),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.precision,
-        "data": "synthetic",
-        "config": {"workload": "MARS seq_len=8 bs=32/GPU %s fwd+distmat (BASELINE configs[1]): 256x128 frames, VMGN "
-                               "ResNet50x2-branch + 2 graph layers, %s distmat vs resident %d x 4096 gallery" %
-                               (args.precision, args.metric, GALLERY_ROWS),
-                   "global_batch": B * world, "seq_len": S, "frames_per_step": B * S * world,
-                   "gallery_rows_per_gpu": hi - lo, "parallelism": "dp%d" % world, "hip_graph": bool(args.graph),
-                   "ranks": world, "collective_backend": ("rccl" if backend == "nccl" else backend),
-                   "devices_visible": torch.cuda.device_count(), "library": os.path.basename(_hip.LIB_PATH),
-                   "per_rank_ms_per_step": [round(x, 3) for x in per_rank_ms],
-                   "clip_batches_rotated": NCLIPS, "clip_bytes_rotated": NCLIPS * B * S * 3 * 256 * 128 * 4},
+    result.update({
         "ms_per_step_blocks": [round(x, 3) for x in block_ms],
         "host_issue_ms_per_step": round(host_issue_ms, 3),
         "host_issue": {"what": "wall time to enqueue one step (forward launches + match stage) with nothing waited for, mean of %d steps; "
@@ -859,7 +910,7 @@ def main():
                        "ms_per_step": round(host_issue_ms, 3), "frac_of_step": round(host_issue_ms / (1e3 * elapsed / args.steps), 3),
                        "cpus_allowed": len(os.sched_getaffinity(0))},
         "ms_per_step_median_of_blocks": round(sorted([1e3 * elapsed / args.steps] + block_ms)[2], 3),
-    }
+    })
     if multi:
         # the ranking step of the sharded evaluation on this batch, once, outside the timed region: per-shard top-50 + candidate
         # merge (parallel.sharded_topk) against a single-process top-50 over the whole gallery on rank 0

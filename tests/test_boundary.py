@@ -199,58 +199,88 @@ def test_missing_library_fails_loudly(monkeypatch):
     assert not _hip.available()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchreid"), reason="reference tree only exists in the build container")
-def test_reference_overlay_resolves_out_of_scope_modules():
+# What the reference's driver (train_vidreid_xent_htri.py) imports from torchreid, module by module ("*" = a star import).
+DRIVER_IMPORTS = {
+    "torchreid": ("data_manager", "metrics", "lr_scheduler", "transforms", "models"),
+    "torchreid.dataset_loader": ("VideoDataset",),
+    "torchreid.losses": ("CrossEntropyLabelSmooth", "TripletLoss", "DeepSupervision"),
+    "torchreid.utils.iotools": ("save_checkpoint", "check_isfile"),
+    "torchreid.utils.avgmeter": ("AverageMeter",),
+    "torchreid.utils.logger": ("Logger",),
+    "torchreid.utils.torchtools": ("set_wd", "cur_time"),
+    "torchreid.utils.reidtools": ("visualize_ranked_results", "calc_splits"),
+    "torchreid.utils.re_ranking": ("re_ranking",),
+    "torchreid.utils.model_complexity": ("compute_model_complexity",),
+    "torchreid.samplers": "*",
+    "torchreid.optimizers": ("init_optim",),
+}
+# the modules this build leaves to the reference, with the names the driver takes from them
+REFERENCE_ONLY = {
+    "data_manager": (), "dataset_loader": ("VideoDataset",), "transforms": (), "lr_scheduler": (), "optimizers": ("init_optim",),
+    "utils/iotools": ("save_checkpoint", "check_isfile"), "utils/avgmeter": ("AverageMeter",), "utils/logger": ("Logger",),
+    "utils/model_complexity": ("compute_model_complexity",),
+}
+# modules this build provides: the stand-in tree has them too, so that the tests see ours win over the reference's
+SHADOWED = ("models/__init__", "metrics/__init__", "losses/__init__", "samplers", "utils/torchtools", "utils/reidtools",
+            "utils/re_ranking")
+
+
+def stand_in_reference(root):
+    """A stand-in for a checkout of the reference at ``root``: its package layout (torchreid/, torchreid/utils/), a stub of
+    every module this build leaves to the reference (defining the names the driver imports from it), and a stub of every
+    module this build shadows (which must never be the one imported)."""
+    for rel in ("__init__", "utils/__init__") + tuple(REFERENCE_ONLY) + SHADOWED:
+        path = root / "torchreid" / (rel + ".py")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        body = "ORIGIN = 'reference'\n" + "".join("class %s:\n    pass\n" % n for n in REFERENCE_ONLY.get(rel, ()))
+        if rel in SHADOWED:
+            body += "raise ImportError('the reference module %s was imported: this build shadows it')\n" % rel
+        path.write_text(body)
+    return root
+
+
+def test_reference_overlay_resolves_out_of_scope_modules(tmp_path):
     """With AGRL_REFERENCE_ROOT set, sub-modules this build does not provide fall through to the reference tree
     while models/metrics/losses stay ours (route A)."""
+    ref = stand_in_reference(tmp_path / "reference")
     code = (
         "import torchreid, torchreid.models, torchreid.metrics, torchreid.lr_scheduler, torchreid.optimizers;"
         "import torchreid.utils.avgmeter, torchreid.utils.reidtools;"
         "print(torchreid.models.__file__); print(torchreid.lr_scheduler.__file__);"
         "print(torchreid.utils.avgmeter.__file__); print(torchreid.utils.reidtools.__file__)"
     )
-    env = dict(os.environ, AGRL_REFERENCE_ROOT="/root/reference", PYTHONPATH=os.path.join(ROOT, "agrl.pytorch_amd"))
-    out = subprocess.check_output(["python", "-c", code], env=env, cwd="/tmp").decode().split()
-    assert "agrl.pytorch_amd" in out[0] and out[1].startswith("/root/reference")
-    assert out[2].startswith("/root/reference") and "agrl.pytorch_amd" in out[3]
+    env = dict(os.environ, AGRL_REFERENCE_ROOT=str(ref), PYTHONPATH=os.path.join(ROOT, "agrl.pytorch_amd"))
+    out = subprocess.check_output([sys.executable, "-c", code], env=env, cwd=str(tmp_path)).decode().split()
+    assert "agrl.pytorch_amd" in out[0] and out[1].startswith(str(ref))
+    assert out[2].startswith(str(ref)) and "agrl.pytorch_amd" in out[3]
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/train_vidreid_xent_htri.py"), reason="reference tree only exists in the build container")
-def test_driver_import_block_under_overlay():
-    """INTEGRATION.md route A: the reference driver's own import block (train_vidreid_xent_htri.py:1-29, read from the
-    reference at test time) executes with this package first on PYTHONPATH -- in particular the names it takes from the
-    modules this build shadows (set_wd, cur_time, visualize_ranked_results, calc_splits, re_ranking, the samplers' star
-    names). tensorboardX / torchvision / h5py are absent from this image and stubbed."""
+def test_driver_import_block_under_overlay(tmp_path):
+    """INTEGRATION.md route A: the reference driver's import block (every torchreid import of train_vidreid_xent_htri.py,
+    DRIVER_IMPORTS) executes with this package first on PYTHONPATH and the reference behind it -- in particular the names it
+    takes from the modules this build shadows (set_wd, cur_time, visualize_ranked_results, calc_splits, re_ranking, the
+    samplers' star names) come from this build, the rest from the reference (a stand-in tree here)."""
+    ref = stand_in_reference(tmp_path / "reference")
+    block = "".join("from %s import %s\n" % (mod, names if names == "*" else ", ".join(names)) for mod, names in DRIVER_IMPORTS.items())
     code = r'''
-import sys, types
-for name in ("tensorboardX", "torchvision", "torchvision.transforms", "torchvision.transforms.functional", "h5py"):
-    sys.modules[name] = types.ModuleType(name)
-sys.modules["tensorboardX"].SummaryWriter = object
-sys.modules["torchvision"].transforms = sys.modules["torchvision.transforms"]
-sys.modules["torchvision.transforms"].functional = sys.modules["torchvision.transforms.functional"]
-def _stub_attr(n):
-    if n.startswith("__"):
-        raise AttributeError(n)
-    return type(n, (), {})
-sys.modules["torchvision.transforms"].__getattr__ = _stub_attr
-for cls in ("ToPILImage", "Resize", "RandomHorizontalFlip", "ToTensor", "Normalize", "Compose"):
-    setattr(sys.modules["torchvision.transforms"], cls, type(cls, (), {}))   # what the reference's transforms.py star-imports
-import scipy.misc, sklearn.metrics._base      # APIs the reference's 2019 pins still had (scipy<1.2, scikit-learn<0.24)
-scipy.misc.imsave = lambda *a, **k: None
-sys.modules["sklearn.metrics.base"] = sklearn.metrics._base
-src = open("/root/reference/train_vidreid_xent_htri.py").read().split("parser = argparse.ArgumentParser")[0]
+import os, sys
+block, ref = sys.argv[1], sys.argv[2]
 ns = {}
-exec(compile(src, "driver_imports", "exec"), ns)
+exec(compile(block, "driver_imports", "exec"), ns)
 import torchreid.utils.torchtools as tt, torchreid.utils.reidtools as rt, torchreid.samplers as sm
 assert "agrl.pytorch_amd" in tt.__file__ and "agrl.pytorch_amd" in rt.__file__ and "agrl.pytorch_amd" in sm.__file__
 for name in ("set_wd", "cur_time", "visualize_ranked_results", "calc_splits", "re_ranking", "compute_model_complexity",
              "save_checkpoint", "AverageMeter", "Logger", "init_optim", "np", "torch", "random", "RandomSampler",
              "RandomIdentitySampler", "TripletLoss", "CrossEntropyLabelSmooth", "DeepSupervision", "models", "metrics"):
     assert name in ns, name
+for name in ("compute_model_complexity", "save_checkpoint", "AverageMeter", "Logger", "init_optim"):
+    assert sys.modules[ns[name].__module__].__file__.startswith(ref), name
+for name in ("set_wd", "cur_time", "visualize_ranked_results", "calc_splits", "re_ranking", "RandomIdentitySampler", "TripletLoss"):
+    assert "agrl.pytorch_amd" in sys.modules[ns[name].__module__].__file__, name
 print("ok")
 '''
-    env = dict(os.environ, AGRL_REFERENCE_ROOT="/root/reference", PYTHONPATH=os.path.join(ROOT, "agrl.pytorch_amd"))
-    out = subprocess.check_output(["python", "-c", code], env=env, cwd="/tmp").decode()
+    env = dict(os.environ, AGRL_REFERENCE_ROOT=str(ref), PYTHONPATH=os.path.join(ROOT, "agrl.pytorch_amd"))
+    out = subprocess.check_output([sys.executable, "-c", code, block, str(ref)], env=env, cwd=str(tmp_path)).decode()
     assert out.strip().endswith("ok")
 
 

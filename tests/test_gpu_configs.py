@@ -105,7 +105,7 @@ def test_bench_self_launches_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "8", "--sustain-seconds", "0", "--profile-steps", "1"], env=env, cwd=root,
+                          "--batch", "8", "--sustain-seconds", "0", "--profile-steps", "1", "--full"], env=env, cwd=root,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -132,7 +132,7 @@ def test_rccl_path_on_one_gpu():
                MASTER_PORT="29631", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
                           "--sustain-seconds", "0", "--profile-steps", "1", "--no-modes", "--no-accuracy", "--no-config5", "--no-config4",
-                          "--no-cpu-baseline"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                          "--no-cpu-baseline", "--full"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     r = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
     cfg = r["config"]
@@ -155,7 +155,7 @@ def test_bench_config3_eight_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                          "--batch", "32", "--sustain-seconds", "0", "--profile-steps", "1", "--dist-timeout", "1200"], env=env, cwd=root,
+                          "--batch", "32", "--sustain-seconds", "0", "--profile-steps", "1", "--dist-timeout", "1200", "--full"], env=env, cwd=root,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1]

@@ -2,7 +2,7 @@
 step's time: python tools/trunk_launches.py  (environment switches apply)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-accuracy",
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-accuracy",
                       "--no-config5", "--no-config4", "--no-modes", "--sustain-seconds", "0"], capture_output=True, text=True, check=True).stdout
 d = json.loads(out.strip().splitlines()[-1])
 t = d["roofline_hbm_bound_trunk"]
