@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from bounds import check_rounded, half_ulp, n_acc_for, poisoned_outputs, U32
 from lp16 import LP16, LP_DTYPE
 import torch.nn.functional as F
 
@@ -31,6 +32,144 @@ def nhwc(x, dtype):
     return x.permute(0, 2, 3, 1).contiguous().to(dtype).to(DEV)
 
 
+# ---- element-by-element bounds (tests/bounds.py) against a float64 CPU reference of each kernel's stated arithmetic
+FULL_REF_FLOPS = 8e9   # above this (exact + magnitude GEMMs), a deterministic subset of output pixels, always all channels
+
+
+def bound_pixels(M, K, Cout, seed=0, tile=128):
+    """Every output pixel (flat n, oh, ow) when the float64 reference is cheap; otherwise the ragged last tile, the first and
+    last row of every 64- and 128-row tile and a seeded random sample."""
+    if 4.0 * M * K * Cout <= FULL_REF_FLOPS:
+        return torch.arange(M)
+    m = torch.arange(M)
+    keep = (m % 64 == 0) | (m % 64 == 63) | (m >= (M // tile) * tile)
+    g = torch.Generator().manual_seed(seed)
+    keep[torch.randint(0, M, (256,), generator=g)] = True
+    return m[keep]
+
+
+def conv_exact(x, w, b, stride=1, pad=0, res=None, relu=False, pixels=None):
+    """float64 relu(conv(x, w) + b + res) and sum |x||w| + |b| + |res| at output pixels ``pixels`` (flat n, oh, ow; default all)
+    -> exact (P, Cout), mag (P, Cout), pixels, coords (P, 3). x NCHW and res NCHW hold what the kernel reads (16-bit values as
+    float), w OIHW, b fp32."""
+    N, Cin, H, W = x.shape
+    Cout, _, R, S = w.shape
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    pix = torch.arange(N * Ho * Wo) if pixels is None else pixels
+    n, oh, ow = pix // (Ho * Wo), pix % (Ho * Wo) // Wo, pix % Wo
+    xp = F.pad(x.detach().cpu().double(), (pad, pad, pad, pad))
+    wm = w.detach().cpu().double().permute(0, 2, 3, 1).reshape(Cout, -1)
+    b64 = b.detach().cpu().double()
+    exact, mag = [], []
+    for lo in range(0, pix.numel(), 2048):
+        sl = slice(lo, lo + 2048)
+        rows = oh[sl, None] * stride + torch.arange(R)
+        cols = ow[sl, None] * stride + torch.arange(S)
+        a = xp[n[sl, None, None], :, rows[:, :, None], cols[:, None, :]].reshape(rows.shape[0], -1)   # (P, R, S, Cin) patches
+        exact.append(a @ wm.t() + b64)
+        mag.append(a.abs() @ wm.abs().t() + b64.abs())
+    exact, mag = torch.cat(exact), torch.cat(mag)
+    if res is not None:
+        r = res.detach().cpu().double()[n, :, oh, ow]
+        exact, mag = exact + r, mag + r.abs()
+    if relu:
+        exact = exact.relu()
+    return exact, mag, pix, torch.stack([n, oh, ow], 1)
+
+
+def check_conv(got_nhwc, x, w, b, stride=1, pad=0, res=None, relu=False, name="", out_dtype=None, n_acc=None, pixels="auto"):
+    """check_rounded of an NHWC conv output against conv_exact; returns (worst ratio, exact-match fraction)."""
+    out_dtype = LP_DTYPE if out_dtype is None else out_dtype
+    N, Ho, Wo, Cout = got_nhwc.shape
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    if isinstance(pixels, str):
+        pixels = bound_pixels(N * Ho * Wo, K, Cout)
+    exact, mag, pix, coords = conv_exact(x, w, b, stride, pad, res, relu, pixels)
+    got = got_nhwc.detach().cpu().reshape(-1, Cout)[pix]
+    M = N * Ho * Wo
+    edge = ((pix >= (M // 128) * 128)[:, None]) | (torch.arange(Cout) >= (Cout // 128) * 128)[None, :]
+    if n_acc is None:
+        n_acc = n_acc_for(K, 4 if out_dtype == torch.float32 else 16)
+    return check_rounded(got, exact, mag, n_acc, out_dtype, coords=coords, edge=edge, name=name)
+
+
+def check_stem(out_nhwc, x, w, b, out_dtype, n_acc, name):
+    """maxpool3x3/2(ReLU(conv7x7/2(x, w) + b)) in float64 on the operands the kernel multiplies, then one RNE rounding (rounding is
+    monotone: the max of rounded values is the rounded max). The bound of a max is the largest bound in its window."""
+    x64, w64 = x.double(), w.double()
+    exact = F.max_pool2d(F.relu(F.conv2d(x64, w64, bias=b.double(), stride=2, padding=3)), 3, 2, 1)
+    mag = F.max_pool2d(F.conv2d(x64.abs(), w64.abs(), bias=b.double().abs(), stride=2, padding=3), 3, 2, 1)
+    return check_rounded(out_nhwc.permute(0, 3, 1, 2), exact, mag, n_acc, out_dtype, name=name)
+
+
+def check_distmat(got, q, g, metric, precision, name):
+    """Euclidean: qn + gn - 2 sum q_op g_op with fp32 norms of the unrounded rows and q_op, g_op the rows in the operand type
+    (distance.py); cosine: 1 - sum qh gh over the kernel's own normalised operand rows. fp32 accumulation, fp32 output.
+    Rows: all, or (large cases) the first / last of every 64-row block, the ragged tail and a seeded sample; all columns."""
+    from torchreid import hip_ops as ops
+    lp = precision != "fp32"
+    dt = LP_DTYPE if lp else torch.float32
+    m, D = q.shape
+    n = g.shape[0]
+    rows = bound_pixels(m, D, n)
+    if metric == "euclidean":
+        q64, g64 = q.double().cpu(), g.double().cpu()
+        qo, go = q.cpu().to(dt).double(), g.cpu().to(dt).double()
+        qn, gn = (q64 * q64).sum(1), (g64 * g64).sum(1)
+        exact = qn[rows, None] + gn[None, :] - 2 * qo[rows] @ go.t()
+        mag = qn[rows, None] + gn[None, :] + 2 * qo[rows].abs() @ go.abs().t()
+    else:
+        km = ops.k_multiple(dt)
+        qh = ops.row_l2_normalize(q.to(DEV), True, dt, km).double().cpu()
+        gh = ops.row_l2_normalize(g.to(DEV), True, dt, km).double().cpu()
+        exact = 1 - qh[rows] @ gh.t()
+        mag = 1 + qh[rows].abs() @ gh.abs().t()
+    edge = (rows >= (m // 256) * 256)[:, None] | (torch.arange(n) >= (n // 256) * 256)[None, :]
+    return check_rounded(got.detach().cpu()[rows], exact, mag, n_acc_for(D, 16 if lp else 4), torch.float32, edge=edge, name=name)
+
+
+def bins(splits, H):
+    return [((j * H) // n, -(-((j + 1) * H) // n)) for n in splits for j in range(n)]
+
+
+def check_conv_pool(pooled, pooled_lp, x_nhwc, w_ohwi, b, res_nhwc, splits, mean, name, frames=4):
+    """Pooled epilogue: the kernel pools its own correctly rounded ReLU activations (fp32 sums over the quarter bins, then / count
+    for means) and the 16-bit copy is the one RNE rounding of that fp32 result. The reference pools the float64 activations rounded
+    to 16 bits; an activation whose pre-rounding value lies within delta of a rounding boundary (or of 0 under the ReLU) may sit one
+    16-bit step the other way: that step, and only for such activations, is the slack. A few frames (first, last, seeded)."""
+    N, H, W, Cin = x_nhwc.shape
+    Cout = w_ohwi.shape[0]
+    g = torch.Generator().manual_seed(N + Cout)
+    fr = torch.unique(torch.cat([torch.tensor([0, N - 1]), torch.randint(0, N, (frames - 2,), generator=g)]))
+    pix = (fr[:, None] * H * W + torch.arange(H * W)).reshape(-1)
+    x = x_nhwc.detach().cpu().float().permute(0, 3, 1, 2)
+    w = w_ohwi.detach().cpu().float().permute(0, 3, 1, 2)
+    r = res_nhwc.detach().cpu().float().permute(0, 3, 1, 2)
+    pre, mag, _, _ = conv_exact(x, w, b, res=r, pixels=pix)
+    delta = n_acc_for(Cin) * U32 * mag
+    a = pre.relu().to(LP_DTYPE).double()
+    dev = torch.maximum(((pre + delta).relu().to(LP_DTYPE).double() - a).abs(), (a - (pre - delta).relu().to(LP_DTYPE).double()).abs())
+    a, dev = a.view(-1, H, W, Cout), dev.view(-1, H, W, Cout)
+    ref, amag, slack, cnt = [], [], [], []
+    for lo, hi in bins(splits, H):
+        ref.append(a[:, lo:hi].sum((1, 2)))
+        amag.append(a[:, lo:hi].abs().sum((1, 2)))
+        slack.append(dev[:, lo:hi].sum((1, 2)))
+        cnt.append((hi - lo) * W)
+    ref, amag, slack = torch.stack(ref, 1), torch.stack(amag, 1), torch.stack(slack, 1)
+    n_acc = max(cnt) + 3
+    if mean:
+        c = torch.tensor(cnt, dtype=torch.float64)[None, :, None]
+        ref, amag, slack = ref / c, amag / c, slack / c
+    got = pooled.detach().cpu()[fr]
+    check_rounded(got, ref, amag, n_acc, torch.float32, slack=slack, name=name + " pooled")
+    if pooled_lp is not None:
+        check_rounded(pooled_lp.detach().cpu()[fr], ref, amag, n_acc, LP_DTYPE, slack=slack, name=name + " pooled 16-bit")
+        # ... and it is the one rounding of the fp32 pooled value itself
+        check_rounded(pooled_lp, pooled.double(), torch.zeros_like(pooled, dtype=torch.float64), 0, LP_DTYPE, min_exact_frac=1.0,
+                      name=name + " 16-bit copy of the pooled value")
+
+
 CONV_CASES = [
     # N, H, W, Cin, Cout, R, stride, residual, relu
     (3, 10, 7, 64, 64, 1, 1, False, True),      # ragged M (210 pixels), small N tile
@@ -49,6 +188,7 @@ CONV_CASES = [
 @pytest.mark.parametrize("dtype", [torch.float32, LP_DTYPE])
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_bn_act(case, dtype):
+    """Operands in ``dtype``, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding to ``dtype``."""
     from torchreid import hip_ops as ops
     N, H, W, Cin, Cout, R, stride, use_res, relu = case
     g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
@@ -67,13 +207,15 @@ def test_conv_bn_act(case, dtype):
         ref = ref + res
     if relu:
         ref = F.relu(ref)
-    out = ops.conv_bn_act(nhwc(x, dtype), w.permute(0, 2, 3, 1).contiguous().to(dtype).to(DEV), b.to(DEV), stride, pad,
-                          relu, residual=None if res is None else nhwc(res, dtype))
+    with poisoned_outputs():
+        out = ops.conv_bn_act(nhwc(x, dtype), w.permute(0, 2, 3, 1).contiguous().to(dtype).to(DEV), b.to(DEV), stride, pad,
+                              relu, residual=None if res is None else nhwc(res, dtype))
     torch.cuda.synchronize()
     got = out.float().permute(0, 3, 1, 2)
     e = rel_err(got, ref)
     print("conv", case, dtype, "rel err %.3e" % e)
     assert e < (1e-5 if dtype == torch.float32 else 1e-2)
+    check_conv(out, x, w, b, stride, pad, res, relu, name="conv_bn_act %s" % (case,), out_dtype=dtype)
 
 
 WIDE_CASES = [
@@ -91,6 +233,7 @@ WIDE_CASES = [
                                   # tile's first k-tile is requested in front of the stores); ragged last M tile; 1 / 3 k-tiles
                                   (81, 16, 8, 64, 2048, False, True), (90, 16, 8, 192, 1024, False, False)])
 def test_conv_wide_tile(case, tile, monkeypatch):
+    """16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; bitwise equal to the narrow tile."""
     from torchreid import hip_ops as ops
     N, H, W, Cin, Cout, use_res, relu = case
     g = torch.Generator().manual_seed(sum(case[:5]))
@@ -110,7 +253,8 @@ def test_conv_wide_tile(case, tile, monkeypatch):
         pytest.skip("256-channel tiles need Cout % 256 == 0")
     monkeypatch.setenv("AGRL_IGEMM_WIDE", tile)
     _hip.reload_options()
-    wide = ops.conv_bn_act(*args, **kw)
+    with poisoned_outputs():
+        wide = ops.conv_bn_act(*args, **kw)
     monkeypatch.setenv("AGRL_IGEMM_WIDE", "0")
     _hip.reload_options()
     narrow = ops.conv_bn_act(*args, **kw)
@@ -118,6 +262,7 @@ def test_conv_wide_tile(case, tile, monkeypatch):
     e = rel_err(wide.float().permute(0, 3, 1, 2), ref)
     print("wide conv", case, "rel err %.3e" % e)
     assert e < 1e-2
+    check_conv(wide, x, w, b, 1, 0, res, relu, name="wide conv %s tile %s" % (case, tile))
     # same fp32 accumulation order per output (k ascending in 32-deep MFMA steps) -> identical bf16 results
     assert torch.equal(wide, narrow)
 
@@ -125,7 +270,8 @@ def test_conv_wide_tile(case, tile, monkeypatch):
 @pytest.mark.parametrize("cnext", [64, 128])
 @pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 10, 7), (5, 64, 32)])
 def test_bottleneck_tail(shape, cnext):
-    """conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_tail.hip) against the
+    """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; z from the rounded out.
+    conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_tail.hip) against the
     two separate igemm launches (bitwise: same fp32 accumulation order, same roundings) and the fp32 reference."""
     from torchreid import hip_ops as ops
     N, H, W = shape
@@ -141,7 +287,8 @@ def test_bottleneck_tail(shape, cnext):
     dw3 = w3.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     dw1 = w1.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     assert ops.bottleneck_tail_supported(dy2, dw3, dw1)
-    out, z = ops.bottleneck_tail(dy2, dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
+    with poisoned_outputs():
+        out, z = ops.bottleneck_tail(dy2, dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
     out2 = ops.conv_bn_act(dy2, dw3, b3.to(DEV), 1, 0, True, residual=dres)
     z2 = ops.conv_bn_act(out2, dw1, b1.to(DEV), 1, 0, True)
     torch.cuda.synchronize()
@@ -149,6 +296,9 @@ def test_bottleneck_tail(shape, cnext):
     print("bottleneck tail", shape, "out %.3e z %.3e" % (e1, e2))
     assert e1 < 1e-2 and e2 < 1e-2
     assert torch.equal(out, out2) and torch.equal(z, z2)
+    check_conv(out, y2, w3, b3, res=res, relu=True, name="tail out %s" % (shape,))
+    # stage 2 against the kernel's OWN stage-1 output: a legitimate one-ulp flip of out does not loosen the bar on z
+    check_conv(z, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name="tail z %s" % (shape,))
     if cnext != 64:
         return
     # first-block form: the shortcut is the block's 1x1 downsample conv of x0, computed in the same pass
@@ -168,7 +318,8 @@ def test_bottleneck_tail(shape, cnext):
 @pytest.mark.parametrize("cnext", [64, 128])
 @pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 8, 24), (9, 64, 32)])
 def test_bottleneck_block(shape, cnext, monkeypatch):
-    """3x3 conv + conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_block.hip)
+    """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; each from the rounded last.
+    3x3 conv + conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_block.hip)
     against the three separate launches (bitwise: same fp32 accumulation order, same roundings) and the fp32 reference;
     (9, 64, 32) = 288 tiles, more than one per workgroup; also the first-block form with the downsample conv."""
     from torchreid import hip_ops as ops
@@ -187,7 +338,8 @@ def test_bottleneck_block(shape, cnext, monkeypatch):
     ohwi = lambda w: w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     dw2, dw3, dw1 = ohwi(w2), ohwi(w3), ohwi(w1)
     assert ops.bottleneck_block_supported(dz, dw2, 1, dw3, dw1)
-    out, zn = ops.bottleneck_block(dz, dw2, b2.to(DEV), dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
+    with poisoned_outputs():
+        out, zn = ops.bottleneck_block(dz, dw2, b2.to(DEV), dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
     y2s = ops.conv_bn_act(dz, dw2, b2.to(DEV), 1, 1, True)
     out2 = ops.conv_bn_act(y2s, dw3, b3.to(DEV), 1, 0, True, residual=dres)
     z2 = ops.conv_bn_act(out2, dw1, b1.to(DEV), 1, 0, True)
@@ -196,6 +348,10 @@ def test_bottleneck_block(shape, cnext, monkeypatch):
     print("bottleneck block", shape, cnext, "out %.3e z %.3e" % (e1, e2))
     assert e1 < 1e-2 and e2 < 1e-2
     assert torch.equal(out, out2) and torch.equal(zn, z2)
+    # the 3x3 stage is never stored by the fused kernel: its bitwise twin y2s (checked by the equalities above) stands in for it
+    check_conv(y2s, z, w2, b2, 1, 1, relu=True, name="block y2 %s" % (shape,))
+    check_conv(out, y2s.float().permute(0, 3, 1, 2).cpu(), w3, b3, res=res, relu=True, name="block out %s" % (shape,))
+    check_conv(zn, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name="block z %s" % (shape,))
     if cnext != 64:
         return
     x0 = torch.randn((N, 64, H, W), generator=g).to(LP_DTYPE).float()
@@ -215,7 +371,8 @@ def test_bottleneck_block(shape, cnext, monkeypatch):
 
 @pytest.mark.parametrize("shape", [(2, 32, 16), (1, 16, 8), (3, 10, 7), (40, 32, 16)])
 def test_bottleneck_tail_layer2(shape):
-    """Layer-2 form of the fused tail (conv3 128 -> 512 + residual + relu, next conv1 512 -> 128; weights resident in
+    """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; z from the rounded out.
+    Layer-2 form of the fused tail (conv3 128 -> 512 + residual + relu, next conv1 512 -> 128; weights resident in
     registers) against the two separate igemm launches (bitwise) and the fp32 reference; (40, 32, 16) = 320 tiles, more
     than one per workgroup (prefetch ring, counted waits), (3, 10, 7) a ragged last tile."""
     from torchreid import hip_ops as ops
@@ -232,7 +389,8 @@ def test_bottleneck_tail_layer2(shape):
     dw3 = w3.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     dw1 = w1.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     assert ops.bottleneck_tail_supported(dy2, dw3, dw1)
-    out, z = ops.bottleneck_tail(dy2, dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
+    with poisoned_outputs():
+        out, z = ops.bottleneck_tail(dy2, dw3, b3.to(DEV), dres, dw1, b1.to(DEV))
     out2 = ops.conv_bn_act(dy2, dw3, b3.to(DEV), 1, 0, True, residual=dres)
     z2 = ops.conv_bn_act(out2, dw1, b1.to(DEV), 1, 0, True)
     torch.cuda.synchronize()
@@ -240,12 +398,15 @@ def test_bottleneck_tail_layer2(shape):
     print("bottleneck tail layer 2", shape, "out %.3e z %.3e" % (e1, e2))
     assert e1 < 1e-2 and e2 < 1e-2
     assert torch.equal(out, out2) and torch.equal(z, z2)
+    check_conv(out, y2, w3, b3, res=res, relu=True, name="tail l2 out %s" % (shape,))
+    check_conv(z, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name="tail l2 z %s" % (shape,))
 
 
 @pytest.mark.parametrize("frames", [1, 3, 40])
 @pytest.mark.parametrize("dims", [(256, 1024, 256), (512, 2048, 512), (256, 1024, 512)])
 def test_bottleneck_seam(dims, frames):
-    """conv3 + residual + relu of a layer-3 / layer-4 block back to back with the next block's conv1 (bottleneck_seam.hip:
+    """Each stage: 16-bit operands, fp32 accumulation from residual + bias, ReLU, one RNE rounding; z from the rounded out.
+    conv3 + residual + relu of a layer-3 / layer-4 block back to back with the next block's conv1 (bottleneck_seam.hip:
     128-pixel tiles, 256-channel chunks handed over through LDS, the pre-packed weights streamed into register rings) against
     the fp32 reference and against the two separate launches. Not bitwise: a chunk's accumulators start as residual + bias, so
     the fp32 summation order differs from (acc + bias) + residual -- the 16-bit outputs may differ by one rounding. 40 frames =
@@ -266,7 +427,8 @@ def test_bottleneck_seam(dims, frames):
     dw1 = w1.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     assert ops.bottleneck_seam_supported(dw3, dw1, frames * H * W)
     packed = ops.bottleneck_seam_pack(dw3, dw1)
-    out, z = ops.bottleneck_seam(dy2, packed, b3.to(DEV), dres, b1.to(DEV), dims)
+    with poisoned_outputs():
+        out, z = ops.bottleneck_seam(dy2, packed, b3.to(DEV), dres, b1.to(DEV), dims)
     out_b, z_b = ops.bottleneck_seam(dy2, packed, b3.to(DEV), dres, b1.to(DEV), dims)
     out2 = ops.conv_bn_act(dy2, dw3, b3.to(DEV), 1, 0, True, residual=dres)
     z2 = ops.conv_bn_act(out2, dw1, b1.to(DEV), 1, 0, True)
@@ -279,6 +441,9 @@ def test_bottleneck_seam(dims, frames):
     assert e1 < tol and e2 < tol
     assert d1 < tol and d2 < tol
     assert torch.equal(out, out_b) and torch.equal(z, z_b)
+    # the bound holds whatever the order of the three fp32 terms (n_acc counts the bias and residual additions)
+    check_conv(out, y2, w3, b3, res=res, relu=True, name="seam out %s x%d" % (dims, frames))
+    check_conv(z, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name="seam z %s x%d" % (dims, frames))
     # a pixel count that is not a whole number of 128-pixel tiles is not taken (10 x 6 frames): the caller runs the two convs
     assert not ops.bottleneck_seam_supported(dw3, dw1, 60)
     with pytest.raises(_hip.HipKernelError):
@@ -289,7 +454,8 @@ def test_bottleneck_seam(dims, frames):
 @pytest.mark.parametrize("case", [(1, 16, 8, 128, 256, True), (3, 16, 8, 256, 256, True), (5, 32, 16, 192, 512, False),
                                   (250, 16, 8, 512, 512, True), (231, 16, 8, 256, 256, True), (7, 32, 16, 128, 128, True), (64, 32, 16, 128, 128, False)])
 def test_conv3x3_packed(case, monkeypatch):
-    """3x3 conv through the four-wave kernel with the pre-packed weight stream (conv3x3_fat.hip) against the fp32 reference and
+    """16-bit operands, fp32 accumulation, acc + bias, ReLU, one RNE rounding.
+    3x3 conv through the four-wave kernel with the pre-packed weight stream (conv3x3_fat.hip) against the fp32 reference and
     against conv_bn_act (same summation order: equal bit for bit). 1 frame = a single workgroup with an absent second block;
     5 frames of 32 x 16 = blocks with real neighbours on all sides (halo rows / columns from the map, zeros at the border);
     250 frames x 512 channels and 231 (an odd block count) also run forced into the two-blocks-per-workgroup form and the half-width form; 128 -> 128 on 32 x 16 maps (layer
@@ -304,7 +470,8 @@ def test_conv3x3_packed(case, monkeypatch):
     dw = w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
     assert ops.conv3x3_packed_supported(dw, H, W)
     packed = ops.conv3x3_pack(dw)
-    out = ops.conv3x3_packed(dx, packed, b.to(DEV), Cout, relu)
+    with poisoned_outputs():
+        out = ops.conv3x3_packed(dx, packed, b.to(DEV), Cout, relu)
     out_b = ops.conv3x3_packed(dx, packed, b.to(DEV), Cout, relu)
     other = ops.conv_bn_act(dx, dw, b.to(DEV), 1, 1, relu)
     torch.cuda.synchronize()
@@ -316,6 +483,7 @@ def test_conv3x3_packed(case, monkeypatch):
     assert e < (3e-3 if LP_DTYPE == torch.float16 else 2e-2)
     assert torch.equal(out, out_b)
     assert torch.equal(out, other)
+    check_conv(out, x, w, b, 1, 1, relu=relu, name="conv3x3 packed %s" % (case,))
     assert not ops.conv3x3_packed_supported(dw, 10, 6)
     if Cout % 256 == 0:   # the other forms of the same kernel family: two blocks per workgroup (the default until late round 5), half-width workgroups
         for var, val in (("AGRL_CONV3X3_FAT_PB", "2"), ("AGRL_CONV3X3_HALF", "1"), ("AGRL_CONV3X3_HALF", "0")):
@@ -333,7 +501,8 @@ def test_conv3x3_packed(case, monkeypatch):
 @pytest.mark.parametrize("case", [(1, 16, 8, 128, 0, 256, True), (3, 10, 6, 256, 0, 512, False), (40, 16, 8, 2048, 0, 512, True),
                                   (37, 16, 8, 1024, 512, 2048, True), (2, 16, 8, 256, 128, 256, True), (250, 16, 8, 1024, 0, 512, True)])
 def test_conv1x1_packed(case):
-    """1x1 conv through the four-wave kernel with the pre-packed weight stream (conv1x1_fat.hip), one source and two (K axis
+    """16-bit operands, fp32 accumulation over [x | x2], acc + bias, ReLU, one RNE rounding.
+    1x1 conv through the four-wave kernel with the pre-packed weight stream (conv1x1_fat.hip), one source and two (K axis
     concatenated: conv3 + downsample conv of a first block), against the fp32 reference and against conv_bn_act /
     conv1x1_dual (same summation order: equal bit for bit). 1 frame = half a pixel tile; 3 frames of 10 x 6 = 180 rows (ragged
     tile, no ReLU); 37 frames = an odd tile count with the layer-4 first-block shape. Every call twice."""
@@ -355,11 +524,13 @@ def test_conv1x1_packed(case):
         dx2 = None
         ref = F.conv2d(x.to(DEV), w.to(DEV), bias=b.to(DEV))
     ref = F.relu(ref) if relu else ref
-    out = ops.conv1x1_packed(dx, packed, b.to(DEV), Cout, relu, x2=dx2)
+    with poisoned_outputs():
+        out = ops.conv1x1_packed(dx, packed, b.to(DEV), Cout, relu, x2=dx2)
     out_b = ops.conv1x1_packed(dx, packed, b.to(DEV), Cout, relu, x2=dx2)
     torch.cuda.synchronize()
     e = rel_err(out.float().permute(0, 3, 1, 2).cpu(), ref.cpu())
     assert e < (3e-3 if LP_DTYPE == torch.float16 else 2e-2), e
+    check_conv(out, torch.cat([x, x2], dim=1) if K2 else x, w, b, relu=relu, name="conv1x1 packed %s" % (case,))
     assert torch.equal(out, out_b)
     if K2 == 0:
         other = ops.conv_bn_act(dx, dw, b.to(DEV), 1, 0, relu)
@@ -384,7 +555,8 @@ STRIDED_DUAL_CASES = [(8, 64, 32, 256, 128, 512, 2), (8, 32, 16, 512, 256, 1024,
 
 @pytest.mark.parametrize("case", STRIDED_DUAL_CASES)
 def test_conv1x1_packed_dual_strided(case):
-    """First block of a strided layer (layers 2 / 3): conv3 + the stride-s 1x1 downsample conv as ONE GEMM over [block input sampled
+    """16-bit operands, fp32 accumulation over [x at the stride | y], acc + (bds + b3 in fp32), ReLU, one RNE rounding.
+    First block of a strided layer (layers 2 / 3): conv3 + the stride-s 1x1 downsample conv as ONE GEMM over [block input sampled
     at the stride | conv2's output] (conv1x1_duo.hip, agrl_conv1x1_packed_dual_strided) against the fp32 reference (two convs + add +
     ReLU), bit for bit against the same kernel fed an explicitly gathered copy of the block input, and -- to the 16-bit rounding of
     the shortcut map that the fused form no longer makes -- against the two launches it replaces. The trunk's two shapes, odd map
@@ -406,7 +578,8 @@ def test_conv1x1_packed_dual_strided(case):
     dual = torch.cat([dwds.view(Cout, -1), dw3.view(Cout, -1)], dim=1).contiguous()
     packed = ops.conv1x1_pack(dual)
     bias = (bds + b3).to(DEV)
-    out = ops.conv1x1_packed_dual_strided(dx, dy, packed, bias, Cout, s, True)
+    with poisoned_outputs():
+        out = ops.conv1x1_packed_dual_strided(dx, dy, packed, bias, Cout, s, True)
     out_b = ops.conv1x1_packed_dual_strided(dx, dy, packed, bias, Cout, s, True)
     gathered = ops.conv1x1_packed(dx[:, ::s, ::s].contiguous(), packed, bias, Cout, True, x2=dy, duo=True)
     shortcut = ops.conv_bn_act(dx, dwds, bds.to(DEV), s, 0, False)
@@ -418,6 +591,7 @@ def test_conv1x1_packed_dual_strided(case):
     assert e < (3e-3 if LP_DTYPE == torch.float16 else 2e-2), e
     assert e2 < (4e-3 if LP_DTYPE == torch.float16 else 3e-2), e2
     assert torch.equal(out, out_b) and torch.equal(out, gathered)
+    check_conv(out, torch.cat([x[:, :, ::s, ::s], y], dim=1), torch.cat([wds, w3], dim=1), bias, relu=True, name="strided dual %s" % (case,))
     with pytest.raises(_hip.HipKernelError):
         ops.call("agrl_conv1x1_packed_dual_strided", ops.ptr(dx), ops.ptr(dy), ops.ptr(packed), ops.ptr(bias), ops.ptr(out), N, Hi, Wi, s,
                  K1 + 64, K2, Cout, 1, None)
@@ -429,7 +603,8 @@ DUO_CASES = [(256, 16, 8, 512, 2048, True, True), (1, 16, 8, 512, 2048, True, Tr
 
 @pytest.mark.parametrize("case", DUO_CASES)
 def test_conv1x1_packed_res(case):
-    """conv3 + identity shortcut + ReLU through the two-workgroups-per-CU kernel (conv1x1_duo.hip) against the fp32 reference and
+    """16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding.
+    conv3 + identity shortcut + ReLU through the two-workgroups-per-CU kernel (conv1x1_duo.hip) against the fp32 reference and
     against conv_bn_act(residual=...) (same summation order, same order of bias / residual / ReLU / rounding: equal bit for bit).
     The full layer-4 shape (2048 tiles: four resident rounds), one frame (8 tiles), a ragged 180-row map without ReLU, an odd tile
     count, no residual with three slabs. Every call twice."""
@@ -448,7 +623,8 @@ def test_conv1x1_packed_res(case):
     if res is not None:
         ref = ref + res.to(DEV)
     ref = F.relu(ref) if relu else ref
-    out = ops.conv1x1_packed_res(dx, packed, b.to(DEV), Cout, dres, relu)
+    with poisoned_outputs():
+        out = ops.conv1x1_packed_res(dx, packed, b.to(DEV), Cout, dres, relu)
     out_b = ops.conv1x1_packed_res(dx, packed, b.to(DEV), Cout, dres, relu)
     other = ops.conv_bn_act(dx, dw, b.to(DEV), 1, 0, relu, residual=dres)
     torch.cuda.synchronize()
@@ -457,6 +633,7 @@ def test_conv1x1_packed_res(case):
     assert e < (3e-3 if LP_DTYPE == torch.float16 else 2e-2), e
     assert torch.equal(out, out_b)
     assert torch.equal(out, other)
+    check_conv(out, x, w, b, res=res, relu=relu, name="conv1x1 duo %s" % (case,))
     with pytest.raises(_hip.HipKernelError):
         ops.call("agrl_conv1x1_packed_res_bn_act", ops.ptr(dx), ops.ptr(packed), ops.ptr(b.to(DEV)), None, ops.ptr(out), N * H * W, K + 64, Cout, 1, None)
 
@@ -527,7 +704,8 @@ def test_conv1x1_duo_persistent_form_is_bit_identical(case, monkeypatch):
 @pytest.mark.parametrize("cfg", [(256, 512, 2048, [4, 2, 1], True), (256, 512, 2048, [1], False), (3, 128, 256, [4, 2, 1], True),
                                  (9, 256, 512, [2, 1], True)])
 def test_conv1x1_packed_res_pool(cfg):
-    """The pool-fused last conv of a layer-4 branch through the two-workgroups-per-CU kernel: pooled sums / means and the 16-bit
+    """Pools of the correctly rounded (acc + bias) + residual, ReLU activations in fp32; the 16-bit copy rounds that once.
+    The pool-fused last conv of a layer-4 branch through the two-workgroups-per-CU kernel: pooled sums / means and the 16-bit
     copy equal BIT FOR BIT to agrl_conv1x1_bn_act_pool's (igemm_wide_kernel's pooled epilogue: same rounded activations, same order
     of the quarter sums) on the layer-4 shapes."""
     from torchreid import hip_ops as ops
@@ -538,7 +716,8 @@ def test_conv1x1_packed_res_pool(cfg):
     b = torch.randn((Cout,), generator=g).to(DEV)
     res = torch.randn((N, 16, 8, Cout), generator=g).to(LP_DTYPE).to(DEV)
     packed = ops.conv1x1_pack(w)
-    pooled, pooled_lp = ops.conv1x1_packed_res_pool(x, packed, b, Cout, res, splits, mean, True)
+    with poisoned_outputs():
+        pooled, pooled_lp = ops.conv1x1_packed_res_pool(x, packed, b, Cout, res, splits, mean, True)
     pooled_b, _ = ops.conv1x1_packed_res_pool(x, packed, b, Cout, res, splits, mean, False)
     ref, ref_lp = ops.conv1x1_bn_act_pool(x, w, b, res, splits, mean, True)
     act = ops.conv_bn_act(x, w, b, 1, 0, True, residual=res)
@@ -558,6 +737,7 @@ def test_conv1x1_packed_res_pool(cfg):
         assert torch.equal(pooled, ref) and torch.equal(pooled_lp, ref_lp)
     else:
         assert rel_err(pooled, ref) < 1e-6 and rel_err(pooled_lp.float(), ref_lp.float()) < 2e-3
+    check_conv_pool(pooled, pooled_lp, x, w, b.cpu(), res, splits, mean, "duo pool conv %s" % (cfg,))
     import ctypes as C
     with pytest.raises(_hip.HipKernelError):   # bins that are not whole quarters
         arr3 = (C.c_int * 1)(3)
@@ -565,10 +745,121 @@ def test_conv1x1_packed_res_pool(cfg):
                  N, 16, 8, Cin, Cout, 1, arr3, 1, 1, None)
 
 
+STRESS_KINDS = ["bnfold", "bias", "residual", "straddle", "tiny"]
+
+
+def stress_operands(kind, N, Cin, H, W, Cout, R=1, use_res=True, seed=0):
+    """16-bit-rounded operands (NCHW / OIHW floats) whose outputs a max-normalised check cannot see into: per-channel scales
+    log-uniform over 2^-12 .. 2^3 (BN folding), channels whose bias or residual dwarfs the accumulator, outputs packed around 0
+    under the ReLU, and channels whose outputs land in the fp16 subnormal range (< 2^-14)."""
+    g = torch.Generator().manual_seed(seed + Cout + Cin)
+    x = torch.randn((N, Cin, H, W), generator=g).to(LP_DTYPE).float()
+    w = torch.randn((Cout, Cin, R, R), generator=g) / np.sqrt(Cin * R * R)
+    b = torch.randn((Cout,), generator=g)
+    res = torch.randn((N, Cout, H, W), generator=g) if use_res else None
+    ch = torch.zeros(Cout, dtype=torch.bool)
+    if kind == "bnfold":
+        sc = torch.exp2(torch.empty(Cout).uniform_(-12, 3, generator=g))
+        w, b = w * sc[:, None, None, None], b * sc
+        if res is not None:
+            res = res * sc[None, :, None, None]
+    elif kind == "bias":
+        ch[::3] = True
+        b[ch] *= 256.0
+    elif kind == "residual":
+        ch[::3] = True
+        if res is not None:
+            res[:, ch] *= 256.0
+        else:
+            b[ch] *= 256.0
+    elif kind == "straddle":
+        w, b = w / 64, b / 256
+        if res is not None:
+            res = res / 64
+    elif kind == "tiny":
+        ch[::7] = True
+        t = 2.0 ** -17
+        w[ch], b[ch] = w[ch] * t, b[ch] * t
+        if res is not None:
+            res[:, ch] *= t
+    w = w.to(LP_DTYPE).float()
+    if res is not None:
+        res = res.to(LP_DTYPE).float()
+    return x, w, b, res
+
+
+def ohwi_dev(w):
+    return w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
+
+
+STRESS_FAMILIES = {
+    # name: shapes (N, H, W, Cin, Cout); ragged M = pixel count not a multiple of the tile, ragged N = Cout not a multiple of
+    # the channel tile, persistent = more tiles than CUs. The pre-packed four-wave kernels (fat, duo, seam) take whole 256- /
+    # 128-channel tiles only: their ragged axis is M.
+    "igemm_1x1": [(3, 10, 7, 256, 200), (81, 16, 8, 64, 256)],          # ragged M + N; persistent walk
+    "igemm_3x3": [(2, 9, 6, 128, 72), (3, 16, 8, 512, 200)],            # ragged M + N (3x3 generic); ragged N (3x3 patch kernel)
+    "wide": [(3, 10, 7, 256, 384), (90, 16, 8, 192, 1024)],            # ragged M; persistent
+    "duo": [(3, 10, 6, 128, 256), (256, 16, 8, 512, 2048)],            # ragged M; persistent (four resident rounds)
+    "fat3x3": [(1, 16, 8, 128, 256), (231, 16, 8, 256, 256)],          # single workgroup; odd block count, more blocks than CUs
+    "tail": [(3, 10, 7, 64, 256), (40, 32, 16, 128, 512)],             # ragged last tile (layer 1); 320 tiles (layer 2)
+    "seam": [(3, 16, 8, 256, 1024), (40, 16, 8, 512, 2048)],           # single workgroup-ish; 40 tiles
+}
+
+
+@pytest.mark.parametrize("kind", STRESS_KINDS)
+@pytest.mark.parametrize("family", list(STRESS_FAMILIES))
+def test_kernel_bounds_on_adversarial_channels(family, kind, monkeypatch):
+    """16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding -- element by element, under
+    poisoned outputs, on inputs whose small channels a max-normalised error cannot see (stress_operands)."""
+    from torchreid import hip_ops as ops
+    for si, (N, H, W, Cin, Cout) in enumerate(STRESS_FAMILIES[family]):
+        name = "%s %s %s" % (family, kind, (N, H, W, Cin, Cout))
+        R = 3 if family in ("igemm_3x3", "fat3x3") else 1
+        use_res = family not in ("igemm_3x3", "fat3x3")
+        x, w, b, res = stress_operands(kind, N, Cin, H, W, Cout, R, use_res, seed=si)
+        dx, dw, db = nhwc(x, LP_DTYPE), ohwi_dev(w), b.to(DEV)
+        dres = None if res is None else nhwc(res, LP_DTYPE)
+        if family == "wide":
+            monkeypatch.setenv("AGRL_IGEMM_WIDE", "3")
+            _hip.reload_options()
+        if family in ("igemm_1x1", "igemm_3x3", "wide"):
+            with poisoned_outputs():
+                out = ops.conv_bn_act(dx, dw, db, 1, R // 2, True, residual=dres)
+            torch.cuda.synchronize()
+            check_conv(out, x, w, b, 1, R // 2, res, True, name=name)
+        elif family == "duo":
+            with poisoned_outputs():
+                out = ops.conv1x1_packed_res(dx, ops.conv1x1_pack(dw), db, Cout, dres, True)
+            torch.cuda.synchronize()
+            check_conv(out, x, w, b, res=res, relu=True, name=name)
+        elif family == "fat3x3":
+            with poisoned_outputs():
+                out = ops.conv3x3_packed(dx, ops.conv3x3_pack(dw), db, Cout, True)
+            torch.cuda.synchronize()
+            check_conv(out, x, w, b, 1, 1, relu=True, name=name)
+        else:   # two-stage: conv3 (Cin -> Cout) + residual + ReLU, then the next conv1 (Cout -> Cin) on the kernel's own stage 1
+            x2, w1, b1, _ = stress_operands(kind, N, Cout, H, W, Cin, 1, False, seed=si + 7)
+            dw1 = ohwi_dev(w1)
+            with poisoned_outputs():
+                if family == "tail":
+                    assert ops.bottleneck_tail_supported(dx, dw, dw1)
+                    out, z = ops.bottleneck_tail(dx, dw, db, dres, dw1, b1.to(DEV))
+                else:
+                    assert ops.bottleneck_seam_supported(dw, dw1, N * H * W)
+                    out, z = ops.bottleneck_seam(dx, ops.bottleneck_seam_pack(dw, dw1), db, dres, b1.to(DEV), (Cin, Cout, Cin))
+            torch.cuda.synchronize()
+            check_conv(out, x, w, b, res=res, relu=True, name=name + " out")
+            check_conv(z, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name=name + " z")
+        if family == "wide":
+            monkeypatch.delenv("AGRL_IGEMM_WIDE")
+            _hip.reload_options()
+
+
 @pytest.mark.parametrize("tile", ["2", "3"])
 @pytest.mark.parametrize("case", [(3, 16, 8, 256, 512), (2, 32, 16, 512, 256), (1, 10, 6, 128, 256)])
 def test_conv_wide_tile_strided(case, tile, monkeypatch):
-    """1x1 stride-2 downsample convs through the wide igemm (gathered pixel rows) against the generic kernel."""
+    """16-bit operands, fp32 accumulation, acc + bias, one RNE rounding.
+    1x1 stride-2 downsample convs through the wide igemm (gathered pixel rows) against the generic kernel."""
     from torchreid import hip_ops as ops
     N, H, W, Cin, Cout = case
     g = torch.Generator().manual_seed(sum(case))
@@ -579,13 +870,15 @@ def test_conv_wide_tile_strided(case, tile, monkeypatch):
     args = (nhwc(x, LP_DTYPE), w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), b.to(DEV), 2, 0, False)
     monkeypatch.setenv("AGRL_IGEMM_WIDE", tile)
     _hip.reload_options()
-    wide = ops.conv_bn_act(*args)
+    with poisoned_outputs():
+        wide = ops.conv_bn_act(*args)
     monkeypatch.setenv("AGRL_IGEMM_WIDE", "0")
     _hip.reload_options()
     narrow = ops.conv_bn_act(*args)
     torch.cuda.synchronize()
     assert rel_err(wide.float().permute(0, 3, 1, 2), ref) < 1e-2
     assert torch.equal(wide, narrow)
+    check_conv(wide, x, w, b, 2, 0, name="wide strided %s tile %s" % (case, tile))
 
 
 DUAL_CASES = [(256, 16, 8, 1024, 512, 2048), (3, 16, 8, 1024, 512, 2048), (90, 16, 8, 128, 64, 512), (81, 16, 8, 512, 256, 256)]
@@ -593,7 +886,8 @@ DUAL_CASES = [(256, 16, 8, 1024, 512, 2048), (3, 16, 8, 1024, 512, 2048), (90, 1
 
 @pytest.mark.parametrize("case", DUAL_CASES)
 def test_conv1x1_dual_source(case):
-    """agrl_conv1x1_dual_bn_act: a first Bottleneck's conv3 + its 1x1 stride-1 downsample conv as ONE GEMM over the
+    """16-bit operands, fp32 accumulation over [x | y2], acc + (bd + b3 in fp32), ReLU, one RNE rounding.
+    agrl_conv1x1_dual_bn_act: a first Bottleneck's conv3 + its 1x1 stride-1 downsample conv as ONE GEMM over the
     concatenated K axis (vmgn.py:56-64), against the fp32 reference of the sum and against the two separate launches (which
     round the shortcut map to bf16 first): full-size layer-4 shape (1024 tiles, persistent walk), ragged M, 3 / 6 / 12 k-tiles,
     the source switch inside the ring."""
@@ -609,7 +903,8 @@ def test_conv1x1_dual_source(case):
     xd, yd = nhwc(x, LP_DTYPE), nhwc(y2, LP_DTYPE)
     wcat = torch.cat([wd.view(Cout, K1), w3.view(Cout, K2)], dim=1).to(LP_DTYPE).to(DEV).contiguous()
     assert ops.conv1x1_dual_supported(xd, yd, wcat)
-    out = ops.conv1x1_dual(xd, yd, wcat, (bd + b3).to(DEV), True)
+    with poisoned_outputs():
+        out = ops.conv1x1_dual(xd, yd, wcat, (bd + b3).to(DEV), True)
     sc = ops.conv_bn_act(xd, wd.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), bd.to(DEV), 1, 0, False)
     sep = ops.conv_bn_act(yd, w3.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), b3.to(DEV), 1, 0, True, residual=sc)
     again = ops.conv1x1_dual(xd, yd, wcat, (bd + b3).to(DEV), True)
@@ -618,6 +913,7 @@ def test_conv1x1_dual_source(case):
     print("dual conv", case, "rel err %.3e (separate launches: %.3e)" % (e, es))
     assert e < 6e-3 and e <= es * 1.05 + 1e-6   # one bf16 rounding of the sum instead of two
     assert torch.equal(out, again)
+    check_conv(out, torch.cat([x, y2], dim=1), torch.cat([wd, w3], dim=1), bd + b3, relu=True, name="dual conv %s" % (case,))
     with pytest.raises(Exception):   # K1 != 2 K2 is not built: loud rejection, the caller keeps the two-launch form
         ops.conv1x1_dual(xd, xd, torch.cat([wcat[:, :K1], wcat[:, :K1]], 1).contiguous(), (bd + b3).to(DEV), True)
 
@@ -625,7 +921,8 @@ def test_conv1x1_dual_source(case):
 @pytest.mark.parametrize("path", ["wide", "persistent"])
 @pytest.mark.parametrize("cfg", [(6, 512, 512, [4, 2, 1], True), (5, 256, 768, [1], False), (4, 2048, 256, [4, 2, 1], True)])
 def test_conv1x1_pool_fused(cfg, path, monkeypatch):
-    """Last conv of a layer4 branch with the frame pooling fused into its epilogue (the 2048-channel map is never
+    """Pools of the correctly rounded (acc + bias) + residual, ReLU activations in fp32; the 16-bit copy rounds that once.
+    Last conv of a layer4 branch with the frame pooling fused into its epilogue (the 2048-channel map is never
     written) against the unfused pair conv_bn_act -> part_pool, both igemm forms."""
     from torchreid import hip_ops as ops
     N, Cin, Cout, splits, mean = cfg
@@ -639,7 +936,8 @@ def test_conv1x1_pool_fused(cfg, path, monkeypatch):
     if path == "wide":
         monkeypatch.setenv("AGRL_IGEMM_WIDE", "1")
         _hip.reload_options()
-    pooled, pooled_lp = ops.conv1x1_bn_act_pool(x, w, b, res, splits, mean, True)
+    with poisoned_outputs():
+        pooled, pooled_lp = ops.conv1x1_bn_act_pool(x, w, b, res, splits, mean, True)
     monkeypatch.delenv("AGRL_IGEMM_WIDE", raising=False)
     _hip.reload_options()
     act = ops.conv_bn_act(x, w, b, 1, 0, True, residual=res)
@@ -656,11 +954,13 @@ def test_conv1x1_pool_fused(cfg, path, monkeypatch):
     print("fused pool conv", cfg, path, "rel err %.3e" % e)
     assert e < 1e-5
     assert rel_err(pooled_lp.float(), ref) < 5e-3
+    check_conv_pool(pooled, pooled_lp, x, w, b.cpu(), res, splits, mean, "fused pool conv %s %s" % (cfg, path))
 
 
 @pytest.mark.parametrize("case", [(2, 32, 16, True), (3, 16, 8, False), (1, 64, 32, True), (5, 16, 24, True)])
 def test_conv3x3_c64_resident_weights(case, monkeypatch):
-    """Layer-1 3x3 (64 -> 64) persistent kernel with all nine taps' weights resident in LDS vs the one-block kernel."""
+    """16-bit operands, fp32 accumulation, acc + bias, ReLU, one RNE rounding.
+    Layer-1 3x3 (64 -> 64) persistent kernel with all nine taps' weights resident in LDS vs the one-block kernel."""
     from torchreid import hip_ops as ops
     N, H, W, relu = case
     g = torch.Generator().manual_seed(N * H + W)
@@ -673,13 +973,15 @@ def test_conv3x3_c64_resident_weights(case, monkeypatch):
     args = (nhwc(x, LP_DTYPE), w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), b.to(DEV), 1, 1, relu)
     monkeypatch.setenv("AGRL_CONV3X3_C64", "1")
     _hip.reload_options()
-    fast = ops.conv_bn_act(*args)
+    with poisoned_outputs():
+        fast = ops.conv_bn_act(*args)
     monkeypatch.setenv("AGRL_CONV3X3_C64", "0")
     _hip.reload_options()
     base = ops.conv_bn_act(*args)
     torch.cuda.synchronize()
     assert rel_err(fast.float().permute(0, 3, 1, 2), ref) < 1e-2
     assert torch.equal(fast, base)
+    check_conv(fast, x, w, b, 1, 1, relu=relu, name="conv3x3 c64 %s" % (case,))
 
 
 WIDE3_CASES = [
@@ -693,6 +995,7 @@ WIDE3_CASES = [
 
 @pytest.mark.parametrize("case", WIDE3_CASES)
 def test_conv3x3_wide_tile(case, monkeypatch):
+    """16-bit operands, fp32 accumulation, acc + bias, ReLU, one RNE rounding; bitwise equal to the narrow kernel."""
     from torchreid import hip_ops as ops
     N, H, W, Cin, Cout, relu = case
     g = torch.Generator().manual_seed(sum(case[:5]))
@@ -705,7 +1008,8 @@ def test_conv3x3_wide_tile(case, monkeypatch):
     args = (nhwc(x, LP_DTYPE), w.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), b.to(DEV), 1, 1, relu)
     monkeypatch.setenv("AGRL_CONV3X3_WIDE", "1")
     _hip.reload_options()
-    wide = ops.conv_bn_act(*args)
+    with poisoned_outputs():
+        wide = ops.conv_bn_act(*args)
     monkeypatch.setenv("AGRL_CONV3X3_WIDE", "0")
     _hip.reload_options()
     narrow = ops.conv_bn_act(*args)
@@ -714,11 +1018,13 @@ def test_conv3x3_wide_tile(case, monkeypatch):
     print("wide 3x3", case, "rel err %.3e" % e)
     assert e < 1e-2
     assert torch.equal(wide, narrow)  # same k order per output -> identical bf16 results
+    check_conv(wide, x, w, b, 1, 1, relu=relu, name="wide 3x3 %s" % (case,))
 
 
 @pytest.mark.parametrize("case", [(385, 16, 8, 128, 512, True), (192, 32, 8, 64, 256, False), (400, 16, 8, 512, 768, True)])
 def test_conv3x3_wide_256_channel_tiles(case, monkeypatch):
-    """The 256-channel-tile form of the two-block 3x3 kernel (64 x 128 wave tiles, two weight slots, out tile over patches +
+    """16-bit operands, fp32 accumulation, acc + bias, ReLU, one RNE rounding.
+    The 256-channel-tile form of the two-block 3x3 kernel (64 x 128 wave tiles, two weight slots, out tile over patches +
     weight ring: layer 4's 512 -> 512 convs at the bench size) is taken when Cout % 256 == 0 and >= 192 such tiles exist:
     odd block count (the last workgroup has one valid block), two blocks per frame, three channel tiles -- against the
     reference conv and BITWISE against the 128-channel-tile form (same k order per output)."""
@@ -732,7 +1038,8 @@ def test_conv3x3_wide_256_channel_tiles(case, monkeypatch):
     monkeypatch.setenv("AGRL_CONV3X3_WIDE", "1")
     monkeypatch.delenv("AGRL_CONV3X3_N128", raising=False)
     _hip.reload_options()
-    t256 = ops.conv_bn_act(*args)
+    with poisoned_outputs():
+        t256 = ops.conv_bn_act(*args)
     monkeypatch.setenv("AGRL_CONV3X3_N128", "1")
     _hip.reload_options()
     t128 = ops.conv_bn_act(*args)
@@ -747,11 +1054,13 @@ def test_conv3x3_wide_256_channel_tiles(case, monkeypatch):
     print("3x3, 256-channel tiles", case, "rel err %.3e" % e)
     assert e < 1e-2
     assert torch.equal(t256, t128)
+    check_conv(t256, x, w, b, 1, 1, relu=relu, name="3x3 256-channel tiles %s" % (case,))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, LP_DTYPE])
 @pytest.mark.parametrize("shape", [(2, 256, 128), (3, 64, 48), (1, 37, 29)])
 def test_stem(shape, dtype):
+    """fp32 operands, a serial fp32 fma chain over the 147 taps, + bias, ReLU, max, one RNE rounding to ``dtype``."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(5)
@@ -759,15 +1068,19 @@ def test_stem(shape, dtype):
     w = torch.randn((64, 3, 7, 7), generator=g) * 0.1
     b = torch.randn((64,), generator=g) * 0.1
     ref = F.max_pool2d(F.relu(F.conv2d(x, w, bias=b, stride=2, padding=3)), 3, 2, 1)
-    out = ops.stem(x.to(DEV), w.permute(0, 2, 3, 1).contiguous().to(DEV), b.to(DEV), dtype)
+    with poisoned_outputs():
+        out = ops.stem(x.to(DEV), w.permute(0, 2, 3, 1).contiguous().to(DEV), b.to(DEV), dtype)
     torch.cuda.synchronize()
     e = rel_err(out.float().permute(0, 3, 1, 2), ref)
     print("stem", shape, dtype, "rel err %.3e" % e)
     assert e < (1e-5 if dtype == torch.float32 else 8e-3)
+    # (the 8e-3 above: that reference does not round; this one models the single rounding of the fp32 result)
+    check_stem(out.cpu(), x, w, b, dtype, 147 + 3, "stem %s %s" % (shape, dtype))
 
 
 @pytest.mark.parametrize("shape", [(2, 256, 128), (3, 64, 48), (1, 37, 29), (1, 224, 112)])
 def test_stem_bf16_mfma(shape):
+    """16-bit pixels and weights, fp32 accumulation (7 k-steps of 32), + bias, ReLU, one RNE rounding, max."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(6)
@@ -777,16 +1090,19 @@ def test_stem_bf16_mfma(shape):
     # the kernel rounds pixels and weights to bf16 and accumulates in fp32: so does the reference here
     ref = F.max_pool2d(F.relu(F.conv2d(x.to(LP_DTYPE).float(), w.to(LP_DTYPE).float(), bias=b, stride=2, padding=3)), 3, 2, 1)
     wpk = ops.pack_stem_weights_lp16(w.permute(0, 2, 3, 1).contiguous().to(DEV))
-    out = ops.stem_lp16(x.to(DEV), wpk, b.to(DEV))
+    with poisoned_outputs():
+        out = ops.stem_lp16(x.to(DEV), wpk, b.to(DEV))
     torch.cuda.synchronize()
     e = rel_err(out.float().permute(0, 3, 1, 2), ref)
     print("stem bf16 mfma", shape, "rel err %.3e" % e)
     assert e < 5e-3  # one bf16 rounding of the output
+    check_stem(out.cpu(), x.to(LP_DTYPE).float(), w.to(LP_DTYPE).float(), b, LP_DTYPE, n_acc_for(224), "stem 16-bit %s" % (shape,))
 
 
 @pytest.mark.parametrize("shape", [(8, 64, 48), (10, 64, 48), (33, 256, 128), (64, 128, 64)])
 def test_stem_16bit_tile_order_and_lds_forms(shape, monkeypatch):
-    """The 16-bit stem walks its tiles frame by frame per XCD from 8 frames on (round 5: HBM fetch 300 -> 101 MB per launch) and keeps
+    """16-bit pixels and weights, fp32 accumulation, + bias, ReLU, one RNE rounding, max -- in every tile order / LDS form.
+    The 16-bit stem walks its tiles frame by frame per XCD from 8 frames on (round 5: HBM fetch 300 -> 101 MB per launch) and keeps
     the patch and the conv tile in separate LDS regions (two barriers per tile): frame counts that give every XCD the same number of
     frames, uneven ones (10, 33: XCDs with one frame more), a grid above the 512 persistent workgroups -- against the fp32 reference,
     and bit for bit against the launch-order / overlaid-region forms (AGRL_STEM_XCD_MAP=0, AGRL_STEM_SPLIT_LDS=0)."""
@@ -799,12 +1115,14 @@ def test_stem_16bit_tile_order_and_lds_forms(shape, monkeypatch):
     ref = F.max_pool2d(F.relu(F.conv2d(x.to(LP_DTYPE).float(), w.to(LP_DTYPE).float(), bias=b, stride=2, padding=3)), 3, 2, 1)
     wpk = ops.pack_stem_weights_lp16(w.permute(0, 2, 3, 1).contiguous().to(DEV))
     dx, db = x.to(DEV), b.to(DEV)
-    out = ops.stem_lp16(dx, wpk, db)
+    with poisoned_outputs():
+        out = ops.stem_lp16(dx, wpk, db)
     again = ops.stem_lp16(dx, wpk, db)
     torch.cuda.synchronize()
     e = rel_err(out.float().permute(0, 3, 1, 2), ref)
     print("stem 16-bit", shape, "rel err %.3e" % e)
     assert e < 5e-3 and torch.equal(out, again)
+    check_stem(out.cpu(), x.to(LP_DTYPE).float(), w.to(LP_DTYPE).float(), b, LP_DTYPE, n_acc_for(224), "stem 16-bit %s" % (shape,))
     for var in ("AGRL_STEM_XCD_MAP", "AGRL_STEM_SPLIT_LDS"):
         monkeypatch.setenv(var, "0")
         _hip.reload_options()
@@ -818,6 +1136,7 @@ def test_stem_16bit_tile_order_and_lds_forms(shape, monkeypatch):
 @pytest.mark.parametrize("dtype", [torch.float32, LP_DTYPE])
 @pytest.mark.parametrize("cfg", [(2, 4, 16, 8, 2048, [4, 2, 1]), (1, 3, 14, 7, 512, [4, 2, 1]), (2, 2, 16, 8, 256, [8, 4, 2, 1]), (1, 2, 16, 8, 256, [4])])
 def test_part_pool(cfg, dtype):
+    """fp32 sums / bin means of the ``dtype`` inputs; nodes_lp is the one RNE rounding of the fp32 nodes."""
     from torchreid import hip_ops as ops
     B, S, h, w, C, splits = cfg
     g = torch.Generator().manual_seed(11)
@@ -825,7 +1144,8 @@ def test_part_pool(cfg, dtype):
     x42 = torch.rand((B * S, C, h, w), generator=g)
     if dtype == LP_DTYPE:
         x41, x42 = x41.to(LP_DTYPE).float(), x42.to(LP_DTYPE).float()
-    gsum, nodes, nodes_lp = ops.part_pool(nhwc(x41, dtype), nhwc(x42, dtype), splits, want_lp=True)
+    with poisoned_outputs():
+        gsum, nodes, nodes_lp = ops.part_pool(nhwc(x41, dtype), nhwc(x42, dtype), splits, want_lp=True)
     torch.cuda.synchronize()
     ref_nodes = O.part_nodes(x42, B, S, splits)
     ref_g = O.global_feature(x41, B, S)
@@ -834,6 +1154,15 @@ def test_part_pool(cfg, dtype):
     e3 = rel_err(nodes_lp.float().view(B, -1, C), ref_nodes)
     print("part_pool", cfg, dtype, "%.3e %.3e %.3e" % (e1, e2, e3))
     assert e1 < 1e-5 and e2 < 1e-5 and e3 < 5e-3
+    # inputs are non-negative: the magnitude sums are the sums themselves
+    nodes64 = O.part_nodes(x42.double(), B, S, splits)
+    gsum64 = x41.double().sum((2, 3))
+    n_acc = h * w + 3
+    check_rounded(nodes.view(B, -1, C), nodes64, nodes64, n_acc, torch.float32, name="part_pool nodes %s" % (cfg,))
+    check_rounded(gsum, gsum64, gsum64, n_acc, torch.float32, name="part_pool gsum %s" % (cfg,))
+    check_rounded(nodes_lp.view(B, -1, C), nodes64, nodes64, n_acc, LP_DTYPE, name="part_pool nodes_lp %s" % (cfg,))
+    check_rounded(nodes_lp, nodes.double(), torch.zeros_like(nodes, dtype=torch.float64), 0, LP_DTYPE, min_exact_frac=1.0,
+                  name="part_pool nodes_lp = rounded nodes %s" % (cfg,))
 
 
 @pytest.mark.parametrize("V", [28, 56, 112, 20])
@@ -1069,24 +1398,29 @@ def test_attention_tail_one_launch(cfg):
 @pytest.mark.parametrize("metric", ["euclidean", "cosine"])
 @pytest.mark.parametrize("shape", [(37, 101, 4096), (5, 300, 96), (130, 257, 2048), (32, 12180, 4096), (8, 3000, 1024), (50, 2500, 512), (20, 2077, 256), (64, 4099, 128)])
 def test_distmat(shape, metric):
+    """fp32 out: qn + gn - 2 q.g (fp32 norms of the unrounded rows) or 1 - qh.gh (the kernel's normalised rows), fp32 accumulation."""
     from torchreid.metrics.distance import hip_distmat_device
     m, n, D = shape
     g = torch.Generator().manual_seed(m)
     q = torch.randn((m, D), generator=g)
     gal = torch.randn((n, D), generator=g)
     ref = O.euclidean_squared(q.double(), gal.double()) if metric == "euclidean" else O.cosine(q.double(), gal.double())
-    got = hip_distmat_device(q.to(DEV), gal.to(DEV), metric, "fp32")
-    got_lp = hip_distmat_device(q.to(DEV), gal.to(DEV), metric, LP16)
+    with poisoned_outputs():
+        got = hip_distmat_device(q.to(DEV), gal.to(DEV), metric, "fp32")
+        got_lp = hip_distmat_device(q.to(DEV), gal.to(DEV), metric, LP16)
     torch.cuda.synchronize()
     e, elp = rel_err(got, ref), rel_err(got_lp, ref)
     print("distmat", shape, metric, "fp32 %.3e bf16 %.3e" % (e, elp))
     assert e < 1e-5 and elp < 1e-2
+    check_distmat(got, q, gal, metric, "fp32", "distmat fp32 %s %s" % (shape, metric))
+    check_distmat(got_lp, q, gal, metric, LP16, "distmat %s %s %s" % (LP16, shape, metric))
 
 
 @pytest.mark.parametrize("metric", ["euclidean", "cosine"])
 @pytest.mark.parametrize("shape", [(2000, 7428, 512), (1793, 8190 + 2, 576)])
 def test_distmat_wide_tile_f32out(shape, metric, monkeypatch):
-    """The full query x gallery form through the 256 x 256 tile with fp32 output (igemm_wide_kernel<65536>: ragged M and N, both
+    """16-bit operands, fp32 accumulation, the euclidean / cosine epilogue in fp32 (see check_distmat).
+    The full query x gallery form through the 256 x 256 tile with fp32 output (igemm_wide_kernel<65536>: ragged M and N, both
     metrics' epilogues) against the tiled igemm form it replaces (AGRL_DISTMAT_TILED=1) and the fp64 oracle."""
     from torchreid.metrics.distance import hip_distmat_device
     m, n, D = shape
@@ -1094,7 +1428,8 @@ def test_distmat_wide_tile_f32out(shape, metric, monkeypatch):
     q, gal = torch.randn((m, D), generator=g), torch.randn((n, D), generator=g)
     ref = O.euclidean_squared(q.double(), gal.double()) if metric == "euclidean" else O.cosine(q.double(), gal.double())
     qd, gd = q.to(DEV), gal.to(DEV)
-    wide = hip_distmat_device(qd, gd, metric, LP16)
+    with poisoned_outputs():
+        wide = hip_distmat_device(qd, gd, metric, LP16)
     monkeypatch.setenv("AGRL_DISTMAT_TILED", "1")
     _hip.reload_options()
     tiled = hip_distmat_device(qd, gd, metric, LP16)
@@ -1105,6 +1440,45 @@ def test_distmat_wide_tile_f32out(shape, metric, monkeypatch):
     d = (wide - tiled).abs().max().item() / tiled.abs().max().item()
     print("distmat wide f32out", shape, metric, "vs fp64 %.3e, vs tiled %.3e" % (e, d))
     assert e < 1e-2 and d < 1e-6 and torch.isfinite(wide).all()
+    check_distmat(wide, q, gal, metric, LP16, "distmat wide %s %s" % (shape, metric))
+
+
+@pytest.mark.parametrize("out_dtype", [torch.float32, LP_DTYPE])
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("shape", [(37, 100, 64), (5, 2048, 1), (300, 513, 8), (3, 96, 256)])
+def test_row_l2_normalize_bound(shape, normalize, out_dtype):
+    """y = x / max(||x||, 1e-12) (fp32 norm) or y = x, one RNE rounding to ``out_dtype``; padding columns up to ``pad_to`` exactly 0.
+    Rows of very different scales (2^-20 ... 2^10: 16-bit subnormals to near the fp16 range), a zero row."""
+    from torchreid import hip_ops as ops
+    R, C, pad_to = shape
+    g = torch.Generator().manual_seed(R + C)
+    x = torch.randn((R, C), generator=g) * torch.exp2(torch.randint(-20, 11, (R, 1), generator=g).float())
+    x[R // 2] = 0
+    with poisoned_outputs():
+        y = ops.row_l2_normalize(x.to(DEV), normalize, out_dtype, pad_to)
+    torch.cuda.synchronize()
+    ld = -(-C // pad_to) * pad_to
+    assert tuple(y.shape) == (R, ld) and y.dtype == out_dtype
+    assert torch.equal(y[:, C:].float().cpu(), torch.zeros((R, ld - C)))
+    x64 = x.double()
+    exact = x64 / x64.norm(dim=1, keepdim=True).clamp(min=1e-12) if normalize else x64
+    n_acc = n_acc_for(C) if normalize else 0
+    check_rounded(y[:, :C], exact, exact.abs(), n_acc, out_dtype, name="row_l2_normalize %s %s %s" % (shape, normalize, out_dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, LP_DTYPE])
+@pytest.mark.parametrize("shape", [(37, 4096), (130, 100), (5, 2048), (64, 7)])
+def test_row_sqnorm_bound(shape, dtype):
+    """sum x^2 of the ``dtype`` rows in fp32 (fma chains, then a wavefront tree), fp32 output."""
+    from torchreid import hip_ops as ops
+    R, C = shape
+    g = torch.Generator().manual_seed(R * C)
+    x = (torch.randn((R, C), generator=g) * torch.exp2(torch.randint(-6, 7, (R, 1), generator=g).float())).to(dtype)
+    with poisoned_outputs():
+        sq = ops.row_sqnorm(x.to(DEV))
+    torch.cuda.synchronize()
+    ex = x.double().pow(2).sum(1)
+    check_rounded(sq, ex, ex, n_acc_for(C), torch.float32, name="row_sqnorm %s %s" % (shape, dtype))
 
 
 @pytest.mark.parametrize("cfg", [(8, 16, 8, 512, 512, 3, 1, 1, False), (8, 16, 8, 2048, 512, 1, 1, 0, False), (6, 16, 8, 512, 2048, 1, 1, 0, True),
@@ -1583,7 +1957,7 @@ def test_distmat_wide_tile_192_columns(shape, metric, monkeypatch):
     shapes above select the 256-column tile. Here: the MARS shape (1980 x 12 180: 512 tiles of 192 columns = two exact rounds, the
     heuristic's own choice; 12 180 = 63 x 192 + 84, ragged), a second ragged N the heuristic also sends there, and a small matrix
     on which the tile is FORCED (AGRL_DISTMAT_TILE_N=192) -- each against the 256-column tile (bit-identical: same k order per
-    output element), the tiled igemm form and the fp64 oracle."""
+    output element), the tiled igemm form and the fp64 oracle. Contract: 16-bit operands, fp32 accumulation, fp32 epilogue."""
     from torchreid.metrics.distance import hip_distmat_device
     m, n, D = shape
     g = torch.Generator().manual_seed(n + m)
@@ -1595,7 +1969,8 @@ def test_distmat_wide_tile_192_columns(shape, metric, monkeypatch):
     for tile in ("192", "256"):
         monkeypatch.setenv("AGRL_DISTMAT_TILE_N", tile)
         _hip.reload_options()
-        out[tile] = hip_distmat_device(qd, gd, metric, LP16)
+        with poisoned_outputs():
+            out[tile] = hip_distmat_device(qd, gd, metric, LP16)
     monkeypatch.delenv("AGRL_DISTMAT_TILE_N")
     monkeypatch.setenv("AGRL_DISTMAT_TILED", "1")
     _hip.reload_options()
@@ -1609,6 +1984,7 @@ def test_distmat_wide_tile_192_columns(shape, metric, monkeypatch):
     assert torch.isfinite(out["192"]).all() and e < 1e-2 and d < 1e-6
     assert torch.equal(out["192"], out["256"])
     assert torch.equal(auto, out["192"])
+    check_distmat(out["192"], q, gal, metric, LP16, "distmat 192-column tile %s %s" % (shape, metric))
 
 
 @pytest.mark.parametrize("metric", ["euclidean", "cosine"])
