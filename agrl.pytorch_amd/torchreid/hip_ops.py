@@ -46,10 +46,6 @@ def switch(name, default='1'):
     return v
 
 
-def switch_on(name, default='1'):
-    return switch(name, default) != '0'
-
-
 _hip.RELOAD_HOOKS.append(_SWITCHES.clear)
 
 
@@ -402,7 +398,7 @@ def conv1x1_dual_supported(x1, x2, w_cat):
     """The two-source pointwise GEMM exists for bf16, K1 == 2 K2, K1 % 64 == 0, Cout % 256 == 0 (layer-4 first blocks)."""
     K1, K2 = x1.shape[-1], x2.shape[-1]
     return (x1.dtype == LP_DTYPE and x2.dtype == LP_DTYPE and K1 == 2 * K2 and K1 % 64 == 0
-            and w_cat.shape[0] % 256 == 0 and x1.shape[:-1] == x2.shape[:-1] and switch_on('AGRL_HIP_FUSE_DS'))
+            and w_cat.shape[0] % 256 == 0 and x1.shape[:-1] == x2.shape[:-1])
 
 
 def conv1x1_dual(x1, x2, w_cat, bias, relu=True):
@@ -446,17 +442,12 @@ def conv1x1_bn_act_pool(x, w_ohwi, bias, residual, splits, mean, want_lp, relu=T
 SEAM_SHAPES = ((256, 1024, 256), (512, 2048, 512), (256, 1024, 512))
 
 
-def seam_enabled():
-    """AGRL_HIP_FUSE_SEAM=0 runs the layer-3 seams as two launches (A/B)."""
-    return switch_on('AGRL_HIP_FUSE_SEAM')
-
-
 def bottleneck_seam_supported(w3, w1_next, pixels=None):
     """conv3 + residual -> next conv1 back to back (agrl_bottleneck_seam): 16-bit weights of a layer-3 / layer-4 seam, and --
     when ``pixels`` is given -- a pixel count made of whole 128-pixel tiles (16 x 8 frames)."""
     return (w3.dtype == LP_DTYPE and w1_next.dtype == LP_DTYPE and w3.dim() == 4 and tuple(w3.shape[1:3]) == (1, 1)
             and (w3.shape[3], w3.shape[0], w1_next.shape[0]) in SEAM_SHAPES and tuple(w1_next.shape[1:]) == (1, 1, w3.shape[0])
-            and (pixels is None or pixels % 128 == 0) and switch_on('AGRL_HIP_FUSE_SEAM'))
+            and (pixels is None or pixels % 128 == 0))
 
 
 def bottleneck_seam_pack(w3, w1_next):
@@ -495,8 +486,8 @@ def bottleneck_seam(y2, packed, b3, residual, b1_next, dims):
 
 
 def conv3x3_packed_enabled():
-    """AGRL_HIP_CONV3X3_PACKED=0 runs the layer-3 / layer-4 3x3 convs through conv_bn_act (A/B; bit-identical results)."""
-    return switch_on('AGRL_HIP_CONV3X3_PACKED')
+    """Always True: the models run every packed 3x3 weight through conv3x3_packed. Kept for bench.py's labels."""
+    return True
 
 
 def conv3x3_packed_supported(w_ohwi, H=None, W=None):
@@ -534,11 +525,6 @@ def conv3x3_packed(x, packed, bias, Cout, relu=True):
     with _dev(x):
         call("agrl_conv3x3_packed_bn_act", ptr(x), ptr(packed), ptr(bias), ptr(out), N, H, W, Cin, Cout, 1 if relu else 0, _stream(x))
     return out
-
-
-def conv1x1_packed_enabled():
-    """AGRL_HIP_CONV1X1_PACKED=0 runs the layer-3 / layer-4 1x1 convs through conv_bn_act / conv1x1_dual (A/B; bit-identical)."""
-    return switch_on('AGRL_HIP_CONV1X1_PACKED')
 
 
 def conv1x1_packed_supported(w):
@@ -603,15 +589,9 @@ def conv1x1_packed_dual_strided(x, x2, packed, bias, Cout, stride, relu=True):
     return out
 
 
-def conv1x1_duo_enabled():
-    """AGRL_HIP_CONV1X1_DUO=0 runs the pool-fused last conv of a layer-4 branch through conv1x1_bn_act_pool and layer 4's conv1s through
-    conv1x1_packed / conv_bn_act (A/B; bit-identical)."""
-    return switch_on('AGRL_HIP_CONV1X1_DUO')
-
-
 def conv1x1_packed_res(x, packed, bias, Cout, residual, relu=True):
     """act(x @ W^T + bias + residual) over pixel rows, weights from conv1x1_pack: conv3 / bn3 + identity shortcut + ReLU of a
-    Bottleneck (vmgn.py:56-64), or with ``residual=None`` a plain conv1 / bn1 / relu (vmgn.py:48-50), through the two-workgroups-per-CU kernel (csrc/conv1x1_duo.hip; layer 4's conv1s are faster here back to back -- 2048 -> 512 69 us against conv1x1_fat_kernel's 73 -- but not inside the step, and stay where they were; with a residual 115.6 against conv_bn_act's 122.4 us back to back, 117 / 119.5 inside a block: also routed here, AGRL_HIP_CONV1X1_DUO_RES=0 = off). -> (N,H,W,Cout) 16-bit NHWC."""
+    Bottleneck (vmgn.py:56-64), or with ``residual=None`` a plain conv1 / bn1 / relu (vmgn.py:48-50), through the two-workgroups-per-CU kernel (csrc/conv1x1_duo.hip; layer 4's conv1s: 2048 -> 512 69 us against conv1x1_fat_kernel's 73 back to back; with a residual 115.6 against conv_bn_act's 122.4 us back to back, 117 / 119.5 inside a block). -> (N,H,W,Cout) 16-bit NHWC."""
     N, H, W, K = x.shape
     M = N * H * W
     assert x.dtype == LP_DTYPE and x.is_contiguous() and packed.numel() == 2 * K * Cout
@@ -650,7 +630,7 @@ def bottleneck_tail_supported(y2, w3, w1_next, shortcut_conv=None):
     """The fused conv3(+residual) -> next conv1 kernel exists for the layer-1 and layer-2 shapes in bf16. ``shortcut_conv`` =
     (weight, stride) of the block's downsample conv when the residual is to be computed in the same pass."""
     if (y2.dtype == LP_DTYPE and tuple(w3.shape) == (512, 1, 1, 128) and tuple(w1_next.shape) == (128, 1, 1, 512)
-            and shortcut_conv is None and switch_on('AGRL_HIP_FUSE_TAIL_L2')):
+            and shortcut_conv is None):
         return True  # layer-2 form (weights resident in registers)
     ok = (y2.dtype == LP_DTYPE and tuple(w3.shape) == (256, 1, 1, 64)
           and tuple(w1_next.shape) in ((64, 1, 1, 256), (128, 1, 1, 256)))
@@ -690,8 +670,6 @@ def bottleneck_tail(y2, w3, b3, residual, w1_next, b1_next, shortcut=None):
 def bottleneck_block_supported(z, w2, stride, w3, w1_next, shortcut_conv=None):
     """The fused 3x3 -> conv3(+shortcut) -> next conv1 kernel exists for the layer-1 shapes in bf16 (stride-1 3x3,
     8 x 8-divisible maps). ``shortcut_conv`` as in bottleneck_tail_supported."""
-    if (not switch_on('AGRL_HIP_FUSE_BLOCK')):
-        return False
     ok = (z.dtype == LP_DTYPE and stride == 1 and tuple(w2.shape) == (64, 3, 3, 64) and tuple(w3.shape) == (256, 1, 1, 64)
           and tuple(w1_next.shape) in ((64, 1, 1, 256), (128, 1, 1, 256)) and z.shape[1] % 8 == 0 and z.shape[2] % 8 == 0)
     if shortcut_conv is not None:
@@ -853,11 +831,11 @@ def graph_apply_operand(G, f, out_dtype, presplit=False):
     return out_lp if out_dtype == LP_DTYPE else out
 
 
-TRACKLET_FORM_MIN_B = int(os.environ.get('AGRL_HIP_GCN_TRACKLET_MIN_B', '224'))
+TRACKLET_FORM_MIN_B = 224
 
 
 def graph_tracklet_operand_supported(f):
-    """One workgroup per tracklet needs enough tracklets to fill the chip (B >= 224 by default: measured 90 us against 119 us for the three launches at 256 tracklets, slower below ~190) and the streaming shapes."""
+    """One workgroup per tracklet needs enough tracklets to fill the chip (B >= 224: measured 90 us against 119 us for the three launches at 256 tracklets, slower below ~190) and the streaming shapes."""
     B, V, Cc = f.shape
     return B >= TRACKLET_FORM_MIN_B and V <= 64 and V % 4 == 0 and Cc % 512 == 0
 

@@ -86,7 +86,7 @@ def hip_forward_ganet(model, x, adj, stages=None):
     with torch.no_grad(), ops.f32_split(model.hip_precision == 'bf16x3'):
         frames = x.reshape(B * S, Cc, H, W)
         a = run_stem(frames, pack)
-        a = _run_trunk(a, pack['trunk'], model.hip_fuse_tail)
+        a = _run_trunk(a, pack['trunk'])
         for blk in pack['l4']:
             a = _run_block(a, blk)
         C = a.shape[-1]

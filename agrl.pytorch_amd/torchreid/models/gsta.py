@@ -61,8 +61,6 @@ class GSTASingle(nn.Module):
         from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
         _ops.check_precision(self.hip_precision)
         self.hip_static_weights = False
-        self.hip_fuse_pool = os.environ.get('AGRL_HIP_FUSE_POOL', '1') != '0'
-        self.hip_fuse_tail = os.environ.get('AGRL_HIP_FUSE_TAIL', '1') != '0'
         self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode forward + backward on the HIP kernels
         self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')
         self._hip_packs = {}

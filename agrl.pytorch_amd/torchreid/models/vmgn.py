@@ -178,8 +178,6 @@ class GSTA(nn.Module):
         from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
         _ops.check_precision(self.hip_precision)
         self.hip_static_weights = False
-        self.hip_fuse_pool = os.environ.get('AGRL_HIP_FUSE_POOL', '1') != '0'
-        self.hip_fuse_tail = os.environ.get('AGRL_HIP_FUSE_TAIL', '1') != '0'
         self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode conv trunk (fwd + bwd) on the HIP kernels
         self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')   # 'fp32' exact | 'bf16x3' split-bf16 MFMA
         self.hip_train_tail = os.environ.get('AGRL_HIP_TRAIN_TAIL', '1') != '0'         # tail of the train forward native as well

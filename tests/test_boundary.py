@@ -337,24 +337,26 @@ def test_host_side_helpers_without_gpu():
     assert torch.equal(pool_clips(f, 3, "max"), torch.stack([f[0:3].max(0)[0], f[3:6].max(0)[0]]))
 
 
-def test_host_side_switches_are_cached_until_reload(monkeypatch):
-    """Round-5 review (dispatch sprawl): the Python-side AGRL_HIP_* switches are read from the environment once, like the library's
-    own, instead of once per Bottleneck of every forward; _hip.reload_options() drops the cache together with the library's."""
+def test_attn_tail_switch_is_cached_until_reload(monkeypatch):
+    """Round-5 review (dispatch sprawl): the Python-side AGRL_HIP_* switches (AGRL_HIP_FUSE_ATTN_TAIL here) are read from the environment
+    once, like the library's own, instead of once per forward; _hip.reload_options() drops the cache together with the library's."""
     from torchreid import _hip
     from torchreid import hip_ops as ops
+    S, P, C, B = 8, 7, 2048, 32                    # 32 tracklets: below the tracklet count from which the one-launch tail is taken
     _hip.reload_options()
-    monkeypatch.delenv("AGRL_HIP_FUSE_SEAM", raising=False)
-    assert ops.switch_on("AGRL_HIP_FUSE_SEAM") and ops.seam_enabled()
-    monkeypatch.setenv("AGRL_HIP_FUSE_SEAM", "0")
-    assert ops.seam_enabled()                      # cached: the forward's dispatch does not touch os.environ
+    monkeypatch.delenv("AGRL_HIP_FUSE_ATTN_TAIL", raising=False)
+    monkeypatch.delenv("AGRL_HIP_ATTN_TAIL_MIN_B", raising=False)
+    assert ops.attn_tail_supported(S, P, C) and not ops.attn_tail_supported(S, P, C, B)
+    monkeypatch.setenv("AGRL_HIP_FUSE_ATTN_TAIL", "1")
+    assert not ops.attn_tail_supported(S, P, C, B)   # cached: the forward's dispatch does not touch os.environ
     _hip.reload_options()
-    assert not ops.seam_enabled()
-    monkeypatch.delenv("AGRL_HIP_FUSE_SEAM")
+    assert ops.attn_tail_supported(S, P, C, B)
+    monkeypatch.delenv("AGRL_HIP_FUSE_ATTN_TAIL")
     _hip.reload_options()
-    assert ops.seam_enabled()
+    assert not ops.attn_tail_supported(S, P, C, B)
 
 
-def test_weight_packs_are_cached_per_precision(monkeypatch):
+def test_weight_packs_are_cached_for_every_precision(monkeypatch):
     """pack_weights packs once per (device, precision) and answers from the cache while no parameter / buffer changed -- for every
     precision mode (round 6: a loop variable in the fp16x3 pack once shadowed the cache key, and every forward re-packed: correct
     results at half the speed, visible only in the bench line). Runs without a GPU: the in-loop form of fp16x3 packs with torch ops only."""
@@ -364,24 +366,35 @@ def test_weight_packs_are_cached_per_precision(monkeypatch):
     from torchreid import hip_ops as ops
     from torchreid import models
     from torchreid.models import _vmgn_hip as V
-    monkeypatch.setenv("AGRL_HIP_SPLIT16_PLANES", "0")   # (the plane packs go through the library's pack kernels: GPU only)
-    ops._SWITCHES.clear()
+    monkeypatch.setattr(ops, "split16_planes_available", lambda: False)   # (the plane packs go through the library's pack kernels: GPU only)
     m = models.init_model("vmgn", num_classes=4, loss={"xent", "htri"}, last_stride=1, num_split=4, num_gb=2, num_scale=1,
                           pyramid_part=True, use_pose=True, learn_graph=True)
     m.load_state_dict(recipe_state_dict(m.state_dict(), seed=0))
     m.eval()
     dev = torch.device("cpu")
-    try:
-        with mock.patch("torch.cuda.current_device", return_value=0):
-            for prec in ("fp32", "bf16x3", "fp16x3"):
-                p1 = V.pack_weights(m, dev, prec)
-                assert V.pack_weights(m, dev, prec) is p1, prec
-                assert set(m._hip_packs) >= {(0, prec)} and all(isinstance(k, tuple) for k in m._hip_packs)
-            with torch.no_grad():
-                m.conv1.weight.mul_(1.0)                      # an in-place edit bumps the version: the pack is rebuilt
-            assert V.pack_weights(m, dev, "fp16x3") is not p1
-    finally:
-        ops._SWITCHES.clear()
+    with mock.patch("torch.cuda.current_device", return_value=0):
+        for prec in ("fp32", "bf16x3", "fp16x3"):
+            p1 = V.pack_weights(m, dev, prec)
+            assert V.pack_weights(m, dev, prec) is p1, prec
+            assert set(m._hip_packs) >= {(0, prec)} and all(isinstance(k, tuple) for k in m._hip_packs)
+        with torch.no_grad():
+            m.conv1.weight.mul_(1.0)                      # an in-place edit bumps the version: the pack is rebuilt
+        assert V.pack_weights(m, dev, "fp16x3") is not p1
+
+
+def test_graph_layers_run_the_commuted_form_only(monkeypatch):
+    """hip_graph_layers runs the GraphLayer as (G f) W^T only. commute=False -- the retired Linear -> message pass form, which handed the
+    fp16x3 pack's pre-split weight bytes to an fp32 GEMM and returned wrong embeddings -- raises before anything is launched."""
+    from torchreid import hip_ops as ops
+    from torchreid.models import _vmgn_hip as V
+    launched = []
+    monkeypatch.setattr(ops, "call", lambda name, *args: launched.append(name))
+    C = 64
+    pack = {"dtype": torch.float32, "graph": [{"w": torch.zeros((C, C)), "scale": torch.ones(C), "shift": torch.zeros(C), "gamma": 0.1,
+                                               "slope": 0.1, "use_pose": False, "learn_graph": True}]}
+    with pytest.raises(ValueError, match="commuted"):
+        V.hip_graph_layers(torch.zeros((1, 4, C)), None, None, pack, commute=False)
+    assert launched == []
 
 
 def test_split16_weight_packers_follow_their_layout_contract():
