@@ -266,6 +266,19 @@ extern "C" size_t agrl_conv_wgrad_workspace(int F, int H, int W, int Cin, int Co
     return (size_t)(p0.ks > p1.ks ? p0.ks : p1.ks) * Cout * R * S * Cin * sizeof(float);   // enough for either arithmetic mode
 }
 
+// The plan agrl_conv_wgrad runs for these arguments: plan[0..3] = {tile rows (output channels), tile columns (input channels),
+// pixel slices ks, 32-pixel k-tiles per slice}. No launch; what a test needs to know the length of the fp32 summation chains.
+extern "C" int agrl_conv_wgrad_plan(int F, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dtype, int* plan) {
+    AGRL_CHECK_ARG(plan, "agrl_conv_wgrad_plan: null pointer");
+    AGRL_CHECK_ARG(F > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && pad >= 0, "agrl_conv_wgrad_plan: bad shape");
+    AGRL_CHECK_ARG(dtype == AGRL_F32 || dtype == AGRL_F32X3, "agrl_conv_wgrad_plan: dtype must be fp32 (0) or split-bf16 fp32 (2), got %d", dtype);
+    const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
+    AGRL_CHECK_ARG(OH > 0 && OW > 0, "agrl_conv_wgrad_plan: empty output");
+    const WgradPlan pl = wgrad_plan(F * OH * OW, Cin, Cout, R * S, dtype);
+    plan[0] = pl.bm; plan[1] = pl.bn; plan[2] = pl.ks; plan[3] = pl.cps;
+    return 0;
+}
+
 extern "C" int agrl_conv_wgrad(const float* x, const float* dy, float* dw, int F, int H, int W, int Cin, int Cout, int R, int S,
                                int stride, int pad, int dtype, void* workspace, size_t workspace_bytes, agrl_stream_t stream) {
     AGRL_CHECK_ARG(x && dy && dw && workspace, "agrl_conv_wgrad: null pointer");

@@ -1322,6 +1322,14 @@ def conv_wgrad_supported(Cin, Cout):
     return Cin % 4 == 0 and Cout % 4 == 0
 
 
+def conv_wgrad_plan(F_, H, W, Cin, Cout, R, S, stride, pad):
+    """-> (output-channel tile, input-channel tile, pixel slices, 32-pixel k-tiles per slice) agrl_conv_wgrad runs for this shape
+    in the calling thread's arithmetic mode (no launch)."""
+    plan = (C.c_int * 4)()
+    call("agrl_conv_wgrad_plan", F_, H, W, Cin, Cout, R, S, stride, pad, _gemm_code(torch.float32), plan)
+    return tuple(int(v) for v in plan)
+
+
 def conv_wgrad(x, dy, wshape, stride, pad):
     """Weight gradient of a conv from the NHWC activations: x (F,H,W,Cin), dy (F,OH,OW,Cout) fp32 -> dw (Cout,Cin,R,S) fp32
     (the nn.Conv2d.weight.grad layout); exact fp32 or, under ``f32_split``, the split-bf16 arithmetic."""

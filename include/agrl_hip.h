@@ -603,6 +603,9 @@ int agrl_gemm_nt_splitk(const void* x, const void* w, float* y, int M, int K, in
  * operands 16-byte aligned. dtype 0 = exact fp32 MFMA, 2 = split-bf16 (three bf16 MFMAs per product). The pixel axis is split
  * over workgroups; partials live in ``workspace`` (agrl_conv_wgrad_workspace bytes) and are summed in slice order. */
 size_t agrl_conv_wgrad_workspace(int F, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad);
+/* the plan agrl_conv_wgrad runs for these arguments, no launch: plan[0..3] = {output-channel tile, input-channel tile, pixel
+ * slices, 32-pixel k-tiles per slice} (host memory) */
+int agrl_conv_wgrad_plan(int F, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dtype, int* plan);
 int agrl_conv_wgrad(const float* x, const float* dy, float* dw, int F, int H, int W, int Cin, int Cout, int R, int S, int stride,
                     int pad, int dtype, void* workspace, size_t workspace_bytes, agrl_stream_t stream);
 

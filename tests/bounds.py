@@ -50,6 +50,11 @@ def _log(record):
             f.write(json.dumps(record) + "\n")
 
 
+def log_record(record):
+    """Append a measurement that is put on record, not asserted (AGRL_BOUNDS_LOG), e.g. the conditioning of a variance."""
+    _log(record)
+
+
 def check_rounded(got, exact, mag, n_acc, out_dtype, min_exact_frac=0.98, *, slack=None, coords=None, edge=None, name=""):
     """Assert the contract above element by element; return (worst err / bound, exact-match fraction).
 

@@ -123,3 +123,426 @@ def test_poisoned_outputs_fills_and_restores():
     assert torch.empty is real
     with pytest.raises(AssertionError):   # an element nobody wrote fails any bound
         check_rounded(f, torch.zeros(3, 4, dtype=torch.float64), torch.ones(3, 4, dtype=torch.float64), 4, torch.float16)
+
+
+# ---- tests/train_ref.py: the float64 references of the train-step kernels -----------------------------------------------------
+# Each helper against an emulation of the stated arithmetic in torch fp32 (accepted) and against seeded faults (rejected).
+import numpy as np
+
+import train_ref as R
+
+F32 = torch.float32
+
+
+def _wgrad_case(kind="scaled", seed=0, Fr=3, H=9, W=7, Cin=8, Cout=12, Rk=3, stride=1, pad=1):
+    OH, OW = (H + 2 * pad - Rk) // stride + 1, (W + 2 * pad - Rk) // stride + 1
+    x, dy = R.stress_train_operands(kind, (Fr, H, W, Cin), (Fr, OH, OW, Cout), seed)
+    return x, dy, (Rk, stride, pad, OH, OW)
+
+
+def _wgrad_emulated(x, dy, geom, cps, drop_tile=None, drop_slice=None, drop_pixel_tap=None):
+    """agrl_conv_wgrad as stated: slices of ``cps`` 32-pixel k-tiles, one fp32 rounding per 4-pixel step inside a slice, the
+    slice partials added in fp32 in slice order. drop_tile = (slice, k-tile), drop_slice, drop_pixel_tap = (pixel, r, s): faults."""
+    Rk, stride, pad, OH, OW = geom
+    Cin, Cout = x.shape[-1], dy.shape[-1]
+    xp = torch.nn.functional.pad(x.double(), (0, 0, pad, pad, pad, pad))
+    d2 = dy.double().reshape(-1, Cout)
+    M = d2.shape[0]
+    nk = -(-M // 32)
+    ks = -(-nk // cps)
+    dw = torch.zeros((Cout, Cin, Rk, Rk), dtype=F32)
+    for r in range(Rk):
+        for s in range(Rk):
+            xs = xp[:, r:r + stride * OH:stride, s:s + stride * OW:stride].reshape(-1, Cin).clone()
+            if drop_pixel_tap is not None and drop_pixel_tap[1:] == (r, s):
+                xs[drop_pixel_tap[0]] = 0
+            total = torch.zeros((Cout, Cin), dtype=F32)
+            for z in range(ks):
+                acc = torch.zeros((Cout, Cin), dtype=F32)
+                for kt in range(z * cps, min(nk, (z + 1) * cps)):
+                    if drop_tile == (z, kt):
+                        continue
+                    for p0 in range(kt * 32, min(M, kt * 32 + 32), 4):
+                        acc = (acc.double() + d2[p0:p0 + 4].t() @ xs[p0:p0 + 4]).float()
+                if drop_slice != z:
+                    total = total + acc
+            dw[:, :, r, s] = total
+    return dw, ks
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_wgrad_reference_accepts_the_sliced_fp32_sum_and_rejects_seeded_faults(kind):
+    x, dy, geom = _wgrad_case(kind)
+    Rk, stride, pad, OH, OW = geom
+    exact, mag = R.wgrad_ref(x, dy, Rk, Rk, stride, pad)
+    M = dy.shape[0] * OH * OW                  # 189 pixels: 6 k-tiles, the last one partial (29 pixels)
+    cps = 2
+    dw, ks = _wgrad_emulated(x, dy, geom, cps)
+    assert ks == 3 and M % 32
+    n_acc = R.wgrad_chain(ks, cps)
+    worst, _ = check_rounded(dw, exact, mag, n_acc, F32, name="wgrad emulation " + kind)
+    assert worst <= 1.0
+    # the last, partial k-tile of the last slice dropped
+    bad, _ = _wgrad_emulated(x, dy, geom, cps, drop_tile=(ks - 1, -(-M // 32) - 1))
+    with pytest.raises(AssertionError):
+        check_rounded(bad, exact, mag, n_acc, F32, name="last k-tile dropped")
+    # one slice left out of the reduce (sparse_dout: the slice that carries everything)
+    bad, _ = _wgrad_emulated(x, dy, geom, cps, drop_slice=ks - 1)
+    with pytest.raises(AssertionError):
+        check_rounded(bad, exact, mag, n_acc, F32, name="slice left out")
+    # one filter tap dropped in one corner: tap (0, 0) of the last pixel of the last frame (reads x[OH - 2][OW - 2]: inside)
+    bad, _ = _wgrad_emulated(x, dy, geom, cps, drop_pixel_tap=(M - 1, 0, 0))
+    if kind != "dead":                           # (a dead input channel contributes nothing anywhere: still rejected through the live ones)
+        with pytest.raises(AssertionError, match=r"0, 0\)"):
+            check_rounded(bad, exact, mag, n_acc, F32, name="corner tap dropped")
+    # a single small-scale output channel multiplied by 1 + 2^-12
+    if kind == "scaled":
+        small = int(dy.abs().amax((0, 1, 2)).argmin())
+        bad = dw.clone()
+        bad[small] *= 1 + 2.0 ** -12
+        with pytest.raises(AssertionError, match=r"at \(%d, " % small):
+            check_rounded(bad, exact, mag, n_acc, F32, name="small channel scaled")
+        # ... which the max-normalised error of test_gpu_train.py's rel() does not see
+        assert ((bad.double() - exact).abs().max() / exact.abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("cfg", [(3, 3, 1, 1), (3, 3, 2, 1), (1, 1, 2, 0), (7, 7, 2, 3), (1, 1, 1, 0)])
+def test_dgrad_reference_is_the_transposed_conv_and_rejects_a_dropped_corner_tap(cfg):
+    Rk, Sk, stride, pad = cfg
+    g = torch.Generator().manual_seed(Rk + stride)
+    Fr, H, W, Cin, Cout = 2, 9, 7, 8, 12
+    OH, OW = (H + 2 * pad - Rk) // stride + 1, (W + 2 * pad - Sk) // stride + 1
+    w = torch.randn((Cout, Cin, Rk, Sk), generator=g) * R.channel_scales(Cin, 3).view(1, Cin, 1, 1)
+    dy = torch.randn((Fr, OH, OW, Cout), generator=g)
+    exact, mag = R.dgrad_ref(dy, w, stride, pad, H, W)
+    pix = torch.tensor([0, 1, W, H * W - 1, H * W, Fr * H * W - 1, 3 * W + 2])
+    e_p, m_p = R.dgrad_ref(dy, w, stride, pad, H, W, pix=pix)        # the gather form at chosen pixels: the same sums
+    assert (e_p - exact.reshape(-1, Cin)[pix]).abs().max() <= 1e-12 * mag.max() and (m_p - mag.reshape(-1, Cin)[pix]).abs().max() <= 1e-12 * mag.max()
+    # autograd of the same conv in float64 is the same function
+    x64 = torch.zeros((Fr, Cin, H, W), dtype=torch.float64, requires_grad=True)
+    torch.nn.functional.conv2d(x64, w.double(), stride=stride, padding=pad).backward(dy.double().permute(0, 3, 1, 2))
+    assert (x64.grad.permute(0, 2, 3, 1) - exact).abs().max() <= 1e-12 * mag.max()
+    # the fp32 emulation: autograd in fp32 (summation order unknown, chain <= taps Cout)
+    x32 = torch.zeros((Fr, Cin, H, W), requires_grad=True)
+    torch.nn.functional.conv2d(x32, w, stride=stride, padding=pad).backward(dy.permute(0, 3, 1, 2).contiguous())
+    got = x32.grad.permute(0, 2, 3, 1).contiguous()
+    n_acc = Rk * Sk * Cout
+    check_rounded(got, exact, mag, n_acc, F32, name="dgrad fp32")
+    if stride > 1 and Rk == 1:
+        untouched = torch.ones((H, W), dtype=torch.bool)
+        untouched[::stride, ::stride] = False
+        assert (exact[:, untouched] == 0).all() and (mag[:, untouched] == 0).all()
+        bad = got.clone()
+        bad[0, 1, 1, 0] = 1e-30                  # anything at all on a pixel the conv never sampled
+        with pytest.raises(AssertionError, match=r"at \(0, 1, 1, 0\)"):
+            check_rounded(bad, exact, mag, n_acc, F32, name="strided 1x1 untouched pixel")
+    # one tap dropped at the corner pixel (0, 0): the output pixel / tap pair (oy, ox, r, s) = (0, 0, pad, pad)
+    bad = got.double() - torch.einsum("fo,oc->fc", dy[:, 0, 0].double(), w[:, :, pad, pad].double())[:, None, None, :] * \
+        torch.nn.functional.one_hot(torch.tensor(0), H * W).view(1, H, W, 1)
+    with pytest.raises(AssertionError, match=r"at \(\d, 0, 0, \d\)"):
+        check_rounded(bad.float(), exact, mag, n_acc, F32, name="corner tap dropped")
+    # the phase chain of the 3x3 / 2 route: 1, 2 or 4 taps per input pixel
+    if (Rk, stride, pad) == (3, 2, 1):
+        ch = R.dgrad_chain("phase", Cout, H=H, W=W)
+        assert ch.shape == (1, H, W, 1) and float(ch[0, 0, 0, 0]) == 3 + 3 and float(ch[0, 1, 1, 0]) == 4 * 3 + 3
+        check_rounded(got, exact, mag, ch, F32, name="dgrad fp32, phase chain")
+
+
+def test_split_bf16_constant_holds_and_is_not_slack():
+    """C_SPLIT against the recipe emulated in float64 (hi = truncation, lo = RNE bf16 of the exact remainder, three exact
+    products) over random and edge operands: never exceeded, and approached within a factor 4. Operands between 2^-30 and 2^30:
+    the low halves stay normal."""
+    g = torch.Generator().manual_seed(0)
+    n = 1 << 21
+    mant = torch.randint(0, 1 << 23, (2, n), generator=g, dtype=torch.int32)
+    expo = torch.randint(127 - 30, 127 + 30, (2, n), generator=g, dtype=torch.int32)
+    sign = torch.randint(0, 2, (2, n), generator=g, dtype=torch.int32)
+    rnd = ((sign << 31) | (expo << 23) | mant).view(F32)
+    edges = []
+    for e in range(-30, 31, 3):
+        s = 2.0 ** e
+        for m in (0, 1, 0x7FFF, 0x8000, 0x8001, 0xFFFF, 0x10000, 0x10001, 0x7F0000, 0x7F7FFF, 0x7F8000, 0x7FFFFF, 0x00FFFF, 0x017FFF, 0x018000):
+            edges.append(s * (1 + m / float(1 << 23)))          # powers of two, all-ones mantissas, either side of a bf16 boundary
+    ed = torch.tensor(edges, dtype=torch.float64).float()
+    ex, ew = torch.meshgrid(ed, ed, indexing="ij")
+    x = torch.cat([rnd[0], ex.reshape(-1), -ex.reshape(-1)])
+    w = torch.cat([rnd[1], ew.reshape(-1), ew.reshape(-1)])
+    hi, lo = R.split_bf16(x)
+    assert torch.equal(hi.to(torch.bfloat16).float(), hi) and torch.equal(lo.to(torch.bfloat16).float(), lo)
+    assert ((x.double() - hi.double()).abs() < 2.0 ** -7 * x.double().abs()).all()
+    rel = (x.double() * w.double() - R.split_product(x, w)).abs() / (x.double() * w.double()).abs()
+    assert float(rel.max()) <= R.C_SPLIT, float(rel.max())
+    assert float(rel.max()) >= R.C_SPLIT / 4, float(rel.max())
+
+
+def test_split_mode_bound_accepts_three_products_and_rejects_a_missing_cross_term():
+    g = torch.Generator().manual_seed(1)
+    M, K, N = 200, 8, 24
+    x, w = torch.randn((M, K), generator=g), torch.randn((N, K), generator=g)
+    exact, mag = x.double() @ w.double().t(), x.double().abs() @ w.double().abs().t()
+    got = R.split_product(x[:, None, :], w[None, :, :]).sum(2).float()
+    n_acc = R.gemm_chain(K)
+    check_rounded(got, exact, mag, n_acc, F32, slack=R.C_SPLIT * mag, name="split")
+    with pytest.raises(AssertionError):          # ... and the split arithmetic is NOT inside the exact-fp32 bound
+        check_rounded(got, exact, mag, n_acc, F32, name="split against the fp32 bound")
+    for drop in ("lh", "hl"):
+        bad = R.split_product(x[:, None, :], w[None, :, :], drop=drop).sum(2).float()
+        with pytest.raises(AssertionError):
+            check_rounded(bad, exact, mag, n_acc, F32, slack=R.C_SPLIT * mag, name="split, cross term %s missing" % drop)
+
+
+def _colreduce_emulated(y, rpc, nrl):
+    """colreduce_vec_kernel<0> + colreduce_final_kernel<0>: per chunk and row lane an fp32 sum / fma chain, then double."""
+    M, C = y.shape
+    sa, sb = torch.zeros(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
+    for r0 in range(0, M, rpc):
+        for rl in range(nrl):
+            a, b = torch.zeros(C), torch.zeros(C)
+            for r in range(r0 + rl, min(M, r0 + rpc), nrl):
+                a = a + y[r]
+                b = (y[r].double() * y[r].double() + b.double()).float()      # fmaf
+            sa, sb = sa + a.double(), sb + b.double()
+    mu = sa / M
+    return mu.float(), (sb / M - mu * mu).clamp(min=0).float()
+
+
+@pytest.mark.parametrize("kind", ["scaled", "dead", "offset"])
+def test_bn_statistics_reference_accepts_the_chunked_fp32_sums(kind):
+    M, C = 20000, 12
+    x, _ = R.stress_train_operands(kind, (1, M, 1, C), (1, M, 1, 4), seed=2)
+    y = x.view(M, C)
+    chunks, rpc, nrl = R.reduce_plan(M, C)
+    assert (chunks, rpc, nrl) == (417, 48, 16) and R.reduce_chain(M, C) == 3 and R.reduce_plan(700, 12) == (44, 16, 16)
+    assert R.reduce_plan(65536, 64) == (512, 128, 16) and R.reduce_plan(5, 4)[0] == 1 and R.reduce_plan(4096, 2048) == (256, 16, 4)
+    assert R.reduce_plan(100, 702) == (7, 16, 4) and R.reduce_lanes(702) == 0      # the scalar kernel: 4 row lanes
+    mean, var = _colreduce_emulated(y, rpc, nrl)
+    ref, ch = R.bn_stats_ref(y), R.bn_stats_chain(R.reduce_chain(M, C))
+    check_rounded(mean, ref["mean"][0], ref["mean"][1], ch["mean"], F32, name="mean " + kind)
+    check_rounded(var, ref["var"][0], ref["var"][1], ch["var"], F32, name="var " + kind)
+    assert (var >= 0).all()
+    if kind == "dead":
+        assert (var[1::3] == 0).all() and (mean[1::3] == 0).all()
+    bad = mean.clone()
+    c = int(y.abs().amax(0).clamp(min=1e-30).argmin()) if kind != "dead" else 0
+    bad[c] *= 1 + 2.0 ** -12
+    with pytest.raises(AssertionError, match=r"at \(%d,\)" % c):
+        check_rounded(bad, ref["mean"][0], ref["mean"][1], ch["mean"], F32, name="mean, one channel scaled")
+
+
+@pytest.mark.parametrize("n", [1, 2, 4096])
+def test_bn_fold_reference_and_the_unbiased_running_variance(n):
+    g = torch.Generator().manual_seed(n)
+    C = 16
+    mean, var = torch.randn(C, generator=g), torch.rand(C, generator=g) * R.channel_scales(C, 5, -20, 3)
+    var[3] = 0.0
+    gamma, beta = 0.5 + torch.rand(C, generator=g), torch.randn(C, generator=g)
+    rm, rv = torch.randn(C, generator=g), 0.5 + torch.rand(C, generator=g)
+    eps, mom = 1e-5, 0.1
+    e32, m32 = torch.tensor(eps, dtype=F32), torch.tensor(mom, dtype=F32)
+    unb = torch.tensor(n / (n - 1) if n > 1 else 1.0, dtype=torch.float64).float()
+    inv = torch.rsqrt(var + e32)
+    sc = gamma * inv
+    got = {"invstd": inv, "scale": sc, "shift": beta - mean * sc,
+           "running_mean": (m32.double() * mean.double() + (rm * (1 - m32)).double()).float(),
+           "running_var": (m32.double() * (var * unb).double() + (rv * (1 - m32)).double()).float()}
+    ref = R.bn_fold_ref(mean, var, gamma, beta, eps, mom, n, rm, rv)
+    for k, (exact, mag, n_acc) in ref.items():
+        check_rounded(got[k], exact, mag, n_acc, F32, name="%s n=%d" % (k, n))
+    assert torch.isfinite(got["invstd"]).all() and float(ref["invstd"][0][3]) == pytest.approx(1 / np.sqrt(np.float32(eps)), rel=1e-12)
+    if n > 1:   # n / (n - 1) missing from running_var: off by 2 at n = 2, by 2.4e-4 at n = 4096
+        bad = (m32.double() * var.double() + (rv * (1 - m32)).double()).float()
+        exact, mag, n_acc = ref["running_var"]
+        with pytest.raises(AssertionError):
+            check_rounded(bad, exact, mag, n_acc, F32, name="running_var without n / (n - 1)")
+        exact, mag, n_acc = R.bn_fold_ref(mean, var, gamma, beta, eps, mom, n, rm, rv, unbias=False)["running_var"]
+        check_rounded(bad, exact, mag, n_acc, F32, name="the fault against the faulty formula")
+
+
+@pytest.mark.parametrize("cfg", [(7, 12, True, 0.0, True), (5, 4, True, 0.1, False), (9, 20, False, 0.0, True)])
+def test_bn_apply_reference_and_the_sign_mask(cfg):
+    M, C, relu, slope, use_res = cfg
+    g = torch.Generator().manual_seed(M * C)
+    y, res = torch.randn((M, C), generator=g), (torch.randn((M, C), generator=g) if use_res else None)
+    scale, shift = torch.randn(C, generator=g) * R.channel_scales(C, 1), torch.randn(C, generator=g)
+    pre = (y.double() * scale.double() + shift.double()).float()        # fmaf
+    if use_res:
+        pre = pre + res
+    out = torch.where(pre > 0, pre, pre * torch.tensor(slope, dtype=F32)) if relu else pre
+    exact, mag, n_acc = R.bn_apply_ref(y, scale, shift, res, relu, slope)
+    check_rounded(out, exact, mag, n_acc, F32, name="bn_apply")
+    if not relu:
+        return
+    assert (M * C // 4) % 2 == 1, "an odd number of float4s: the last mask byte holds one nibble"
+    mask = R.pack_sign_mask(pre.reshape(-1) > 0)
+    assert mask.numel() == (M * C + 7) // 8 and torch.equal(R.unpack_sign_mask(mask, M * C), pre.reshape(-1) > 0)
+    R.check_sign_mask(mask, out, "mask")
+    shifted = R.pack_sign_mask(torch.roll(pre.reshape(-1) > 0, 1))       # every nibble shifted by one element
+    with pytest.raises(AssertionError, match="mask bytes differ"):
+        R.check_sign_mask(shifted, out, "mask shifted by one element")
+    one = mask.clone()
+    one[-1] ^= 0x10                                                     # a bit in the unused nibble of the last byte
+    with pytest.raises(AssertionError, match="mask bytes differ"):
+        R.check_sign_mask(one, out, "unused nibble set")
+
+
+def test_bn_backward_reference_accepts_the_fp32_formula():
+    g = torch.Generator().manual_seed(4)
+    M, C = 300, 12
+    x, _ = R.stress_train_operands("offset", (1, M, 1, C), (1, M, 1, 4), seed=4)
+    y, dz = x.view(M, C), torch.randn((M, C), generator=g) * R.channel_scales(C, 9)
+    st = R.bn_stats_ref(y)
+    mean, invstd = st["mean"][0].float(), (1 / torch.sqrt(st["var"][0].clamp(min=0) + 1e-5)).float()
+    gamma = 0.5 + torch.rand(C, generator=g)
+    xh = (y - mean) * invstd
+    s1, s2 = dz.sum(0), (dz * xh).sum(0)
+    sums, ch = R.bn_backward_sums_ref(dz, y, mean, invstd), R.bn_backward_sums_chain(M, False)
+    check_rounded(s1, sums["dbeta"][0], sums["dbeta"][1], ch["dbeta"], F32, name="dbeta")
+    check_rounded(s2, sums["dgamma"][0], sums["dgamma"][1], ch["dgamma"], F32, name="dgamma")
+    inv_m = torch.tensor(1.0, dtype=F32) / torch.tensor(float(M), dtype=F32)
+    dy = gamma * invstd * (dz - s1 * inv_m - xh * (s2 * inv_m))
+    exact, mag, n_acc = R.bn_backward_ref(dz, y, mean, invstd, gamma, s1, s2)
+    check_rounded(dy, exact, mag, n_acc, F32, name="bn_backward apply")
+    bad = dy.clone()
+    bad[:, 5] *= 1 + 2.0 ** -12
+    with pytest.raises(AssertionError, match=r", 5\)"):
+        check_rounded(bad, exact, mag, n_acc, F32, name="bn_backward, one channel scaled")
+
+
+@pytest.mark.parametrize("shape", [(2, 9, 7, 5), (1, 2, 2, 3), (2, 16, 8, 4)])
+def test_maxpool_reference_first_maximum_and_its_gradient(shape):
+    g = torch.Generator().manual_seed(sum(shape))
+    x = torch.randn(shape, generator=g).relu()                           # post-ReLU: ties at zero in most windows
+    out, idx = R.maxpool_ref(x)
+    ref = torch.nn.functional.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    assert torch.equal(out, ref)
+    Fr, H, W, C = shape
+    # the recorded tap holds the maximum, and no earlier tap of the window does
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1), value=float("-inf"))
+    for f, oh, ow, c in [(0, 0, 0, 0), (Fr - 1, out.shape[1] - 1, out.shape[2] - 1, C - 1), (0, out.shape[1] // 2, 0, 1)]:
+        win = xp[f, 2 * oh:2 * oh + 3, 2 * ow:2 * ow + 3, c].reshape(-1)
+        first = int(torch.nonzero(win == win.max())[0])
+        assert int(idx[f, oh, ow, c]) == first
+    dout = torch.randn(out.shape, generator=g)
+    dx = R.maxpool_backward_ref(dout, idx, H, W)
+    assert abs(float(dx.double().sum() - dout.double().sum())) < 1e-4 and dx.shape == x.shape
+    zero = torch.zeros(dx.shape, dtype=torch.float64)
+    check_rounded(dx, dx.double(), zero, 0, F32, name="maxpool backward")
+    # the gradient sent to the LAST maximum of a window instead of the first
+    _, idx_last = R.maxpool_ref(x, last=True)
+    assert not torch.equal(idx_last, idx)
+    with pytest.raises(AssertionError):
+        check_rounded(R.maxpool_backward_ref(dout, idx_last, H, W), dx.double(), zero, 0, F32, name="maxpool backward, last maximum")
+    # where the input is positive and unique the two agree: what test_gpu_train.py's comparison was restricted to
+
+
+def test_tail_references_accept_fp32_emulations():
+    g = torch.Generator().manual_seed(8)
+    a_, b_ = torch.randn((5, 7, 64), generator=g), torch.randn((5, 7, 64), generator=g)
+    exact, mag, n_acc = R.axpby_ref(0.9, a_, 0.1, b_)
+    check_rounded(torch.tensor(0.9, dtype=F32) * a_ + torch.tensor(0.1, dtype=F32) * b_, exact, mag, n_acc + 1, F32, name="axpby")
+    Fr, S, h, w, C, splits = 4, 2, 6, 3, 8, (4, 2, 1)
+    dg, dn = torch.randn((Fr // S, C), generator=g), torch.randn((Fr, 7, C), generator=g)
+    x1 = torch.randn((Fr, C, h, w), generator=g, requires_grad=True)
+    x2 = torch.randn((Fr, C, h, w), generator=g, requires_grad=True)
+    gl = x1.view(Fr // S, S, C, h * w).permute(0, 2, 1, 3).reshape(Fr // S, C, -1).mean(2)
+    nodes = torch.cat([torch.nn.functional.adaptive_avg_pool2d(x2, (n, 1)).view(Fr, C, n) for n in splits], 2).transpose(1, 2)
+    ((gl * dg).sum() + (nodes * dn).sum()).backward()
+    (e1, m1, n1), (e2, m2, n2) = R.part_pool_backward_ref(dg, dn, S, h, w, splits)
+    check_rounded(x1.grad.permute(0, 2, 3, 1), e1, m1, n1, F32, name="part pool dx1")
+    check_rounded(x2.grad.permute(0, 2, 3, 1), e2, m2, n2, F32, name="part pool dx2")
+    A, Bm = torch.randn((2, 9, 256), generator=g), torch.randn((2, 9, 256), generator=g)
+    exact, mag, n_acc = R.pair_product_ref(A, Bm)
+    check_rounded(torch.bmm(A, Bm.transpose(1, 2)), exact, mag, 256, F32, name="pair product")
+    assert n_acc == 32 + 2 + 3
+    for n, K in ((16, 702), (4, 5)):
+        z = (3 * torch.randn((n, K), generator=g)).requires_grad_(True)
+        y = torch.randint(0, K, (n,), generator=g)
+        logp = torch.log_softmax(z, 1)
+        q = torch.zeros(n, K).scatter_(1, y[:, None], 1.0) * (1 - 0.1) + 0.1 / K
+        loss = (-q * logp).mean(0).sum()
+        loss.backward()
+        (l64, lb), (d64, db) = R.xent_ref(z.detach(), y, 0.1)
+        zero = torch.zeros_like(d64)
+        check_rounded(z.grad, d64, zero, 0, F32, slack=db, name="xent dlogits")
+        check_rounded(loss.detach().view(1), l64, torch.zeros(1, dtype=torch.float64), 0, F32, slack=lb, name="xent loss")
+        bad = z.grad.clone()
+        bad[1, int(y[1])] += 2.0 ** -12 / n * (1 - 0.1)                   # the target's q off by 2^-12 relative
+        with pytest.raises(AssertionError):
+            check_rounded(bad, d64, zero, 0, F32, slack=db, name="xent dlogits, q wrong")
+
+
+def test_attention_pool_and_triplet_references_accept_fp32_autograd():
+    g = torch.Generator().manual_seed(0)
+    nodes = torch.rand((3, 6, 7, 128), generator=g)
+    nodes[1, 2, 3] = 0                       # an all-zero node: by convention its norm passes no gradient
+    nodes.requires_grad_(True)
+    att = torch.nn.functional.normalize(nodes.norm(p=2, dim=3, keepdim=True), p=1, dim=1)
+    a = (nodes * att).sum(1).mean(1)
+    da = torch.randn(a.shape, generator=g)
+    a.backward(da)
+    exact, mag, n_acc = R.attn_pool_backward_ref(nodes.detach(), da)
+    check_rounded(nodes.grad, exact, mag, n_acc, F32, name="attention pool backward")
+    assert n_acc == 5 * 10 + 3 * 6 + 16 and bool((exact[1, 2, 3] == 0).all() and (mag[1, 2, 3] == 0).all())
+    bad = nodes.grad.clone()
+    bad[2, 5, 6] *= 1 + 2.0 ** -12
+    with pytest.raises(AssertionError, match=r"at \(2, 5, 6, "):
+        check_rounded(bad, exact, mag, n_acc, F32, name="attention pool backward, one node scaled")
+    n, d = 16, 64
+    for soft in (True, False):
+        x = torch.randn((n, d), generator=g).requires_grad_(True)
+        pids = torch.arange(4).repeat_interleave(4)
+        dist = (x.pow(2).sum(1)[:, None] + x.pow(2).sum(1)[None, :] - 2 * x @ x.t()).clamp(min=1e-12).sqrt()
+        same = pids[:, None] == pids[None, :]
+        dap, iap = (dist - 1e9 * (~same)).max(1)
+        dan, ian = (dist + 1e9 * same).min(1)
+        loss = torch.nn.functional.softplus(dap - dan).mean() if soft else (dap - dan + 0.3).clamp(min=0).mean()
+        loss.backward()
+        r = R.triplet_ref(x.detach(), pids, 0.3, soft, dap.detach(), dan.detach(), iap, ian)
+        zero = torch.zeros(n, dtype=torch.float64)
+        check_rounded(x.grad, r["grad"][0], r["grad"][1], r["grad"][2], F32, name="triplet grad")
+        check_rounded(loss.detach().view(1), r["loss"][0], zero[:1], 0, F32, slack=r["loss"][3], name="triplet loss")
+        check_rounded(dap.detach(), r["dist_ap"][0], zero, 0, F32, slack=r["dist_ap"][3], name="triplet d_ap")
+        check_rounded(dan.detach(), r["dist_an"][0], zero, 0, F32, slack=r["dist_an"][3], name="triplet d_an")
+        bad = x.grad.clone()
+        bad[int(iap[0])] += (x.detach()[0] - x.detach()[int(iap[0])]) * 2.0 ** -12 / n     # one scattered term 2^-12 too large
+        if float(dap[0].detach()) > 0 and (soft or float(loss.detach()) > 0):
+            with pytest.raises(AssertionError):
+                check_rounded(bad, r["grad"][0], r["grad"][1], r["grad"][2], F32, name="triplet grad, one term scaled")
+
+
+@pytest.mark.parametrize("cfg", [(3, 56, 256, True), (2, 28, 128, False)])
+def test_graph_matrix_backward_reference_accepts_the_fp32_formulas(cfg):
+    """The kernel's formulas step by step in torch fp32 stay inside the propagated bound; the same with the diagonal passing a
+    gradient (sqrt'(1e-12) on E_ii, what the kernel's convention excludes) or one off-diagonal E off by 2^-10 does not."""
+    B, V, C, use_pose = cfg
+    g = torch.Generator().manual_seed(V + C)
+    f = torch.rand((B, 1, C), generator=g) * 0.2 + 0.05 * torch.randn((B, V, C), generator=g)
+    gp = torch.stack([torch.bmm(f[:, :, z:z + 128], f[:, :, z:z + 128].transpose(1, 2)) for z in range(0, C, 128)], 1)
+    dG = torch.randn((B, V, V), generator=g)
+    exact, slack, live = R.graph_matrix_backward_ref(gp, dG, use_pose)
+    eye = torch.eye(V, dtype=torch.bool)
+    assert bool(live[:, ~eye].all()) and not bool(live[:, eye].any())
+
+    def emulate(diag_gradient=False, scale_one=False):
+        gs = gp.sum(1)
+        n = torch.diagonal(gs, dim1=1, dim2=2)
+        d2 = ((n[:, None, :] + n[:, :, None]) - 2 * gs).clamp(min=1e-12)
+        d = d2.sqrt()
+        S = 2 / (torch.exp(d) + 1)
+        r = S.sum(2, keepdim=True)
+        x = dG * (0.5 if use_pose else 1.0)
+        c = (x * (S / r)).sum(2, keepdim=True)
+        dD = -S * (1 - 0.5 * S) * ((x - c) / r)
+        E = dD / (2 * d)
+        if not diag_gradient:
+            E = torch.where(eye | ~(d2 > 1e-12), torch.zeros_like(E), E)
+        if scale_one:
+            E[0, 1, 2] *= 1 + 2.0 ** -10
+        T = E + E.transpose(1, 2)
+        return 2 * (torch.diag_embed(T.sum(2)) - T)
+    zero = torch.zeros_like(exact)
+    worst, _ = check_rounded(emulate(), exact, zero, 0, F32, slack=slack, name="graph matrix backward")
+    assert worst > 0.01, "the propagated bound is within two orders of what fp32 does"
+    for fault in ({"diag_gradient": True}, {"scale_one": True}):
+        with pytest.raises(AssertionError):
+            check_rounded(emulate(**fault), exact, zero, 0, F32, slack=slack, name="graph matrix backward, fault")

@@ -1,6 +1,11 @@
 """Native train step (BASELINE config 4; reference train(), train_vidreid_xent_htri.py:397-413): the conv trunk's forward
 with batch-statistics BatchNorm and its whole backward on the HIP kernels, against the SAME step computed on the CPU by the
-stock-torch module tree (the reference's arithmetic: nn.Conv2d / nn.BatchNorm2d / autograd)."""
+stock-torch module tree (the reference's arithmetic: nn.Conv2d / nn.BatchNorm2d / autograd).
+
+These 57 tests judge whole nodes and the whole step with one max-normalised number, rel() = max |a - b| / max |b|, mostly
+against fp32 CPU autograd. Kernel by kernel the same train-step kernels are held to elementwise float64 bounds, NaN-poisoned
+outputs and workspaces, adversarial channel scales and run-to-run bitwise equality in tests/test_gpu_train_bounds.py (references
+and chain lengths: tests/train_ref.py)."""
 import numpy as np
 import pytest
 import torch
