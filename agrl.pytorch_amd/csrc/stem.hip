@@ -10,6 +10,7 @@
 // Out-of-range conv positions are stored as 0, which is exact for a max over post-ReLU values whose
 // window always contains at least one in-range element.
 #include "agrl_common.h"
+#include "frames_u8.h"
 
 namespace {
 constexpr int PT_H = 4, PT_W = 8;                // pooled tile
@@ -20,11 +21,13 @@ constexpr int IT_WP = 40;
 constexpr int KTAPS = 147;
 constexpr int POS_PER_THREAD = (NPOS + 15) / 16;  // 10
 
-template <typename TOUT>
-__global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, const float* __restrict__ w,
+// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument): the patch is staged through the normalisation table -- all of a
+// thread's bytes are requested first, then looked up -- and everything behind the staged patch is the fp32 form's code.
+template <typename TOUT, typename TIN, typename... EX>
+__global__ __launch_bounds__(256) void stem_kernel(const TIN* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ bias, TOUT* __restrict__ out,
                                                    int H, int W, int CH, int CW, int PH, int PW, int tiles_w,
-                                                   int tiles_hw) {
+                                                   int tiles_hw, EX... ex) {
     __shared__ __attribute__((aligned(16))) float s_patch[3 * IT_H * IT_WP];
     __shared__ __attribute__((aligned(16))) float s_wc[NPOS * 64];  // weights (147x64) then conv tile (153x64)
 
@@ -36,15 +39,37 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
     const int cr0 = 2 * ph0 - 1, cc0 = 2 * pw0 - 1;  // first conv row/col of the tile
     const int iy0 = 2 * cr0 - 3, ix0 = 2 * cc0 - 3;  // first input row/col of the patch
 
-    const float* xn = x + (size_t)n * 3 * H * W;
-    for (int e = tid; e < 3 * IT_H * IT_WP; e += 256) {
-        const int c = e / (IT_H * IT_WP);
-        const int r = (e / IT_WP) % IT_H;
-        const int q = e % IT_WP;
-        const int iy = iy0 + r, ix = ix0 + q;
-        float v = 0.f;
-        if (q < IT_W && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xn[((size_t)c * H + iy) * W + ix];
-        s_patch[e] = v;
+    const TIN* xn = x + (size_t)n * 3 * H * W;
+    if constexpr (sizeof...(EX) != 0) {
+        const FramesU8 u8 = frames_u8_of(ex...);
+        constexpr int NE = 3 * IT_H * IT_WP, NPASS = (NE + 255) / 256;
+        uint32_t pb[NPASS];  // raw bytes, FRAMES_U8_PAD (the table's zero entry) outside the frame
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i) {
+            const int e = tid + 256 * i;
+            const int c = e / (IT_H * IT_WP);
+            const int r = (e / IT_WP) % IT_H;
+            const int q = e % IT_WP;
+            const int iy = iy0 + r, ix = ix0 + q;
+            pb[i] = FRAMES_U8_PAD;
+            if (e < NE && q < IT_W && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+                pb[i] = xn[((size_t)iy * W + ix) * u8.pixel_stride + (size_t)c * u8.channel_stride];
+        }
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i) {
+            const int e = tid + 256 * i;
+            if (e < NE) s_patch[e] = u8.table[(e / (IT_H * IT_WP)) * FRAMES_U8_ROW + pb[i]];
+        }
+    } else {
+        for (int e = tid; e < 3 * IT_H * IT_WP; e += 256) {
+            const int c = e / (IT_H * IT_WP);
+            const int r = (e / IT_WP) % IT_H;
+            const int q = e % IT_WP;
+            const int iy = iy0 + r, ix = ix0 + q;
+            float v = 0.f;
+            if (q < IT_W && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xn[((size_t)c * H + iy) * W + ix];
+            s_patch[e] = v;
+        }
     }
     // w is (64, 147) row-major (OHWI flattened); stage transposed to [k][o]
     for (int e = tid; e < KTAPS * 64; e += 256) {
@@ -120,22 +145,36 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
 }
 }  // namespace
 
-extern "C" int agrl_stem_conv_bn_relu_maxpool(const float* x, const float* w, const float* bias, void* out,
-                                              int N, int H, int W, int out_dtype, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(x && w && bias && out, "agrl_stem: null pointer");
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "agrl_stem: bad shape N=%d H=%d W=%d", N, H, W);
-    AGRL_CHECK_ARG(out_dtype == AGRL_F32 || out_dtype == AGRL_LP16, "agrl_stem: bad dtype %d", out_dtype);
+template <typename TIN, typename... EX>
+static int launch_stem(const char* who, const TIN* x, const float* w, const float* bias, void* out, int N, int H, int W, int out_dtype,
+                       agrl_stream_t stream, EX... ex) {
+    AGRL_CHECK_ARG(x && w && bias && out, "%s: null pointer", who);
+    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    AGRL_CHECK_ARG(out_dtype == AGRL_F32 || out_dtype == AGRL_LP16, "%s: bad dtype %d", who, out_dtype);
     const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
     const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
     const int tiles_h = cdiv(PH, PT_H), tiles_w = cdiv(PW, PT_W);
     const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "agrl_stem: grid too large");
+    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
     if (out_dtype == AGRL_F32)
-        hipLaunchKernelGGL(stem_kernel<float>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                           (float*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w);
+        hipLaunchKernelGGL((stem_kernel<float, TIN, EX...>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
+                           (float*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, ex...);
     else
-        hipLaunchKernelGGL(stem_kernel<lp16_t>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                           (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w);
-    AGRL_CHECK_LAUNCH("agrl_stem");
+        hipLaunchKernelGGL((stem_kernel<lp16_t, TIN, EX...>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
+                           (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, ex...);
+    AGRL_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int agrl_stem_conv_bn_relu_maxpool(const float* x, const float* w, const float* bias, void* out,
+                                              int N, int H, int W, int out_dtype, agrl_stream_t stream) {
+    return launch_stem("agrl_stem", x, w, bias, out, N, H, W, out_dtype, stream);
+}
+
+extern "C" int agrl_stem_conv_bn_relu_maxpool_u8(const unsigned char* x, const float* table, int layout, const float* w,
+                                                 const float* bias, void* out, int N, int H, int W, int out_dtype,
+                                                 agrl_stream_t stream) {
+    FramesU8 u8;
+    if (frames_u8_args("agrl_stem_u8", table, layout, H, W, &u8)) return 1;
+    return launch_stem("agrl_stem_u8", x, w, bias, out, N, H, W, out_dtype, stream, u8);
 }

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "agrl_common.h"
+#include "frames_u8.h"
 
 namespace {
 constexpr int PT = 8;                 // pooled tile edge
@@ -45,11 +46,17 @@ constexpr int REGION_BYTES = CT_BYTES > PATCH_BYTES ? CT_BYTES : PATCH_BYTES;
 // SPLIT: the patch and the conv tile in SEPARATE LDS regions (12.2 + 36.5 + 30 KB + biases = 78.9 KB: still two workgroups per CU) -- the
 // two barriers that guarded the overlay (sweep done -> conv tile may be written; pool done -> next patch may be written) disappear: a wave
 // that has finished pooling writes its pixels of the next patch while the others still pool, two barriers per tile instead of four.
-template <bool SPLIT>
-__global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restrict__ x, const unsigned char* __restrict__ wpk,
+//
+// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument): a thread requests its pixels' BYTES where the fp32 form requests
+// floats, and turns them into the normalised fp32 values one phase later -- a gather from the 3 KB table (L1-resident; in LDS it would
+// cost the SPLIT form its second workgroup per CU) issued behind the conv-tile barrier, when the bytes have had the whole MFMA sweep to
+// land, and in flight under the pooling. Everything from the LDS write of the patch on is the fp32 form's code on the same values.
+template <bool SPLIT, typename TIN, typename... EX>
+__global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict__ x, const unsigned char* __restrict__ wpk,
                                                         const float* __restrict__ bias, lp16_t* __restrict__ out, int H,
                                                         int W, int CH, int CW, int PH, int PW, int tiles_w, int tiles_hw,
-                                                        int ntiles, int xcd_map) {
+                                                        int ntiles, int xcd_map, EX... ex) {
+    constexpr bool U8 = sizeof...(EX) != 0;
     constexpr int TILES_BYTES = SPLIT ? PATCH_BYTES + CT_BYTES : REGION_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char smem[TILES_BYTES + W_BYTES + 256];
     unsigned char* s_patch = smem;
@@ -71,12 +78,13 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
     // patch: one pixel (3 channels -> 4 bf16) per thread per pass; all loads of all passes are issued together
     constexpr int NPASS = (IT * PWP + NTH - 1) / NTH;  // 4
     float pv[NPASS][3];
+    uint32_t pb[U8 ? NPASS : 1][3];  // uint8 frames: the raw bytes, FRAMES_U8_PAD (the table's zero entry) outside the frame
     auto load_patch = [&](int T) {
         const int n = T / tiles_hw;
         const int trem = T - n * tiles_hw;
         const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
         const int iy0 = 2 * (2 * ph0 - 1) - 3, ix0 = 2 * (2 * pw0 - 1) - 3;
-        const float* xn = x + (size_t)n * 3 * H * W;
+        const TIN* xn = x + (size_t)n * 3 * H * W;
         int td = tid;
         asm volatile("" : "+v"(td));  // per-tile address arithmetic (hoisted out of the tile loop it costs 100 registers)
 #pragma unroll
@@ -84,13 +92,33 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
             const int e = td + NTH * i;
             const int py = e / PWP, px = e - py * PWP;
             const int iy = iy0 + py, ix = ix0 + px;
-            pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
-            if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                const size_t o = (size_t)iy * W + ix;
-                pv[i][0] = xn[o];
-                pv[i][1] = xn[(size_t)H * W + o];
-                pv[i][2] = xn[2 * (size_t)H * W + o];
+            if constexpr (U8) {
+                const FramesU8 u8 = frames_u8_of(ex...);
+                pb[i][0] = pb[i][1] = pb[i][2] = FRAMES_U8_PAD;
+                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const uint32_t o = (uint32_t)(iy * W + ix) * u8.pixel_stride;   // inside one frame: < 3 H W < 2^31 (frames_u8_args)
+                    pb[i][0] = xn[o];
+                    pb[i][1] = xn[o + (uint32_t)u8.channel_stride];
+                    pb[i][2] = xn[o + 2 * (uint32_t)u8.channel_stride];
+                }
+            } else {
+                pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
+                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const size_t o = (size_t)iy * W + ix;
+                    pv[i][0] = xn[o];
+                    pv[i][1] = xn[(size_t)H * W + o];
+                    pv[i][2] = xn[2 * (size_t)H * W + o];
+                }
             }
+        }
+    };
+    auto normalize_patch = [&]() {  // uint8 frames: bytes -> table values (the fp32 form's pv)
+        if constexpr (U8) {
+            const FramesU8 u8 = frames_u8_of(ex...);
+#pragma unroll
+            for (int i = 0; i < NPASS; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pv[i][c] = u8.table[c * FRAMES_U8_ROW + pb[i][c]];
         }
     };
     const int frow = lane & 15, g = lane >> 4;
@@ -120,7 +148,10 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
         return (xcd + 8 * fl) * tiles_hw + (q - fl * tiles_hw);
     };
     int q = xmap ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (q < qlimit) load_patch(tile_of(q));
+    if (q < qlimit) {
+        load_patch(tile_of(q));
+        normalize_patch();
+    }
     for (; q < qlimit; q += qstep) {
         const int T = tile_of(q);
         const int n = T / tiles_hw;
@@ -128,9 +159,11 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
         const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
         const int cr0 = 2 * ph0 - 1, cc0 = 2 * pw0 - 1;
         // ---- this tile's pixels (requested one tile ago) -> bf16 patch in LDS
+        int tw = tid;
+        if constexpr (U8) asm volatile("" : "+v"(tw));  // the uint8 form has no register to spare for hoisted LDS addresses
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
-            const int e = tid + NTH * i;
+            const int e = tw + NTH * i;
             if (e < IT * PWP) {
                 uint2 u;
                 u.x = pack_lp16x2(pv[i][0], pv[i][1]);
@@ -199,6 +232,7 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
             }
         }
         __syncthreads();
+        if (q + qstep < qlimit) normalize_patch();  // uint8 frames: the next tile's bytes have landed under the sweep
 
         // 3x3/2 max pool: thread -> 8 channels (one 16-byte slot) of ONE pooled pixel. The activations are post-ReLU bf16,
         // i.e. non-negative: their bit patterns order like unsigned 16-bit integers, so the maximum is two v_pk_max_u16 per
@@ -231,27 +265,40 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const float* __restri
 }
 }  // namespace
 
-extern "C" int agrl_stem_conv_bn_relu_maxpool_lp16(const float* x, const void* w_packed, const float* bias, void* out,
-                                                   int N, int H, int W, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(x && w_packed && bias && out, "agrl_stem_lp16: null pointer");
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "agrl_stem_lp16: bad shape N=%d H=%d W=%d", N, H, W);
+template <typename TIN, typename... EX>
+static int launch_stem_mfma(const char* who, const TIN* x, const void* w_packed, const float* bias, void* out, int N, int H, int W,
+                            agrl_stream_t stream, EX... ex) {
+    AGRL_CHECK_ARG(x && w_packed && bias && out, "%s: null pointer", who);
+    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
     AGRL_CHECK_ARG((((uintptr_t)w_packed) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
-                   "agrl_stem_lp16: misaligned pointer");
+                   "%s: misaligned pointer", who);
     const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
     const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
     const int tiles_h = cdiv(PH, PT), tiles_w = cdiv(PW, PT);
     const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "agrl_stem_lp16: grid too large");
+    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
     const int wgs = 512;  // two persistent workgroups per CU (67 KB of LDS each)
     const unsigned launch = (unsigned)(grid < wgs ? grid : wgs);
     if (agrl_opts().stem_split_lds != 0)
-        hipLaunchKernelGGL(stem_mfma_kernel<true>, dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
+        hipLaunchKernelGGL((stem_mfma_kernel<true, TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
                        (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w,
-                       (int)grid, agrl_opts().stem_xcd_map != 0);
+                       (int)grid, agrl_opts().stem_xcd_map != 0, ex...);
     else
-        hipLaunchKernelGGL(stem_mfma_kernel<false>, dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
+        hipLaunchKernelGGL((stem_mfma_kernel<false, TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
                        (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w,
-                       (int)grid, agrl_opts().stem_xcd_map != 0);
-    AGRL_CHECK_LAUNCH("agrl_stem_lp16");
+                       (int)grid, agrl_opts().stem_xcd_map != 0, ex...);
+    AGRL_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int agrl_stem_conv_bn_relu_maxpool_lp16(const float* x, const void* w_packed, const float* bias, void* out,
+                                                   int N, int H, int W, agrl_stream_t stream) {
+    return launch_stem_mfma("agrl_stem_lp16", x, w_packed, bias, out, N, H, W, stream);
+}
+
+extern "C" int agrl_stem_conv_bn_relu_maxpool_lp16_u8(const unsigned char* x, const float* table, int layout, const void* w_packed,
+                                                      const float* bias, void* out, int N, int H, int W, agrl_stream_t stream) {
+    FramesU8 u8;
+    if (frames_u8_args("agrl_stem_lp16_u8", table, layout, H, W, &u8)) return 1;
+    return launch_stem_mfma("agrl_stem_lp16_u8", x, w_packed, bias, out, N, H, W, stream, u8);
 }

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "agrl_common.h"
+#include "frames_u8.h"
 
 namespace {
 constexpr int PT = 8;                 // pooled tile edge
@@ -40,10 +41,15 @@ __device__ __forceinline__ uint32_t pack_f16x2(float a, float b) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
-__global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restrict__ x, const unsigned char* __restrict__ wh_pk,
+// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument): as in stem_mfma.hip -- the next tile's BYTES are requested where
+// the fp32 form requests floats, and become the normalised fp32 values through a gather from the 3 KB table issued behind the first
+// channel half's conv-tile barrier (the bytes have had that half's MFMA sweep to land). The rest is the fp32 form's code.
+template <typename TIN, typename... EX>
+__global__ __launch_bounds__(NTH) void stem_split16_kernel(const TIN* __restrict__ x, const unsigned char* __restrict__ wh_pk,
                                                            const unsigned char* __restrict__ wl_pk, const float* __restrict__ bias,
                                                            float* __restrict__ out, float alpha, int H, int W, int CH, int CW, int PH,
-                                                           int PW, int tiles_w, int tiles_hw, int ntiles) {
+                                                           int PW, int tiles_w, int tiles_hw, int ntiles, EX... ex) {
+    constexpr bool U8 = sizeof...(EX) != 0;
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * PATCH_BYTES + CT_BYTES + 2 * W_BYTES + 256];
     unsigned char* s_ph = smem;
     unsigned char* s_pl = smem + PATCH_BYTES;
@@ -65,12 +71,13 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restri
 
     constexpr int NPASS = (IT * PWP + NTH - 1) / NTH;  // 4
     float pv[NPASS][3];
+    uint32_t pb[U8 ? NPASS : 1][3];  // uint8 frames: the raw bytes, FRAMES_U8_PAD (the table's zero entry) outside the frame
     auto load_patch = [&](int T) {
         const int n = T / tiles_hw;
         const int trem = T - n * tiles_hw;
         const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
         const int iy0 = 2 * (2 * ph0 - 1) - 3, ix0 = 2 * (2 * pw0 - 1) - 3;
-        const float* xn = x + (size_t)n * 3 * H * W;
+        const TIN* xn = x + (size_t)n * 3 * H * W;
         int td = tid;
         asm volatile("" : "+v"(td));
 #pragma unroll
@@ -78,13 +85,33 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restri
             const int e = td + NTH * i;
             const int py = e / PWP, px = e - py * PWP;
             const int iy = iy0 + py, ix = ix0 + px;
-            pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
-            if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                const size_t o = (size_t)iy * W + ix;
-                pv[i][0] = xn[o];
-                pv[i][1] = xn[(size_t)H * W + o];
-                pv[i][2] = xn[2 * (size_t)H * W + o];
+            if constexpr (U8) {
+                const FramesU8 u8 = frames_u8_of(ex...);
+                pb[i][0] = pb[i][1] = pb[i][2] = FRAMES_U8_PAD;
+                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const uint32_t o = (uint32_t)(iy * W + ix) * u8.pixel_stride;   // inside one frame: < 3 H W < 2^31 (frames_u8_args)
+                    pb[i][0] = xn[o];
+                    pb[i][1] = xn[o + (uint32_t)u8.channel_stride];
+                    pb[i][2] = xn[o + 2 * (uint32_t)u8.channel_stride];
+                }
+            } else {
+                pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
+                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const size_t o = (size_t)iy * W + ix;
+                    pv[i][0] = xn[o];
+                    pv[i][1] = xn[(size_t)H * W + o];
+                    pv[i][2] = xn[2 * (size_t)H * W + o];
+                }
             }
+        }
+    };
+    auto normalize_patch = [&]() {  // uint8 frames: bytes -> table values (the fp32 form's pv)
+        if constexpr (U8) {
+            const FramesU8 u8 = frames_u8_of(ex...);
+#pragma unroll
+            for (int i = 0; i < NPASS; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pv[i][c] = u8.table[c * FRAMES_U8_ROW + pb[i][c]];
         }
     };
     const int frow = lane & 15, g = lane >> 4;
@@ -99,7 +126,10 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restri
     auto ct_row = [](int pos) { return (pos & ~3) | ((pos & 1) << 1) | ((pos >> 1) & 1); };
 
     int q = blockIdx.x;
-    if (q < ntiles) load_patch(q);
+    if (q < ntiles) {
+        load_patch(q);
+        normalize_patch();
+    }
     for (; q < ntiles; q += G) {
         const int T = q;
         const int n = T / tiles_hw;
@@ -181,6 +211,9 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restri
                 }
             }
             __syncthreads();
+            if constexpr (U8) {
+                if (half == 0 && q + G < ntiles) normalize_patch();  // the next tile's bytes have landed under the sweep
+            }
             // 3x3/2 max pool: thread -> 4 channels (one 16-byte slot) of one pooled pixel
             {
                 const int cq = tq & 7;
@@ -208,29 +241,42 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const float* __restri
 }
 }  // namespace
 
-extern "C" int agrl_stem_split16(const float* x, const void* wh_packed, const void* wl_packed, const float* bias, float* out, int N,
-                                 int H, int W, float w_unscale, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(x && wh_packed && wl_packed && bias && out, "agrl_stem_split16: null pointer");
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "agrl_stem_split16: bad shape N=%d H=%d W=%d", N, H, W);
-    AGRL_CHECK_ARG(((((uintptr_t)wh_packed) | ((uintptr_t)wl_packed) | ((uintptr_t)bias) | ((uintptr_t)out)) & 15) == 0, "agrl_stem_split16: misaligned pointer");
-    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale <= 3.4e38f, "agrl_stem_split16: w_unscale must be a positive finite power of two");
+template <typename TIN, typename... EX>
+static int launch_stem_split16(const char* who, const TIN* x, const void* wh_packed, const void* wl_packed, const float* bias, float* out,
+                               int N, int H, int W, float w_unscale, agrl_stream_t stream, EX... ex) {
+    AGRL_CHECK_ARG(x && wh_packed && wl_packed && bias && out, "%s: null pointer", who);
+    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    AGRL_CHECK_ARG(((((uintptr_t)wh_packed) | ((uintptr_t)wl_packed) | ((uintptr_t)bias) | ((uintptr_t)out)) & 15) == 0, "%s: misaligned pointer", who);
+    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale <= 3.4e38f, "%s: w_unscale must be a positive finite power of two", who);
     {
         int e = 0;
-        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "agrl_stem_split16: w_unscale=%g is not a power of two", (double)w_unscale);
+        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "%s: w_unscale=%g is not a power of two", who, (double)w_unscale);
     }
     const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
     const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
     const int tiles_h = cdiv(PH, PT), tiles_w = cdiv(PW, PT);
     const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "agrl_stem_split16: grid too large");
+    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) {
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
     }
     const unsigned launch = (unsigned)(grid < cus ? grid : cus);   // one persistent workgroup per CU (123 KB of LDS)
-    hipLaunchKernelGGL(stem_split16_kernel, dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x, (const unsigned char*)wh_packed,
-                       (const unsigned char*)wl_packed, bias, out, w_unscale, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, (int)grid);
-    AGRL_CHECK_LAUNCH("agrl_stem_split16");
+    hipLaunchKernelGGL((stem_split16_kernel<TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x, (const unsigned char*)wh_packed,
+                       (const unsigned char*)wl_packed, bias, out, w_unscale, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, (int)grid, ex...);
+    AGRL_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int agrl_stem_split16(const float* x, const void* wh_packed, const void* wl_packed, const float* bias, float* out, int N,
+                                 int H, int W, float w_unscale, agrl_stream_t stream) {
+    return launch_stem_split16("agrl_stem_split16", x, wh_packed, wl_packed, bias, out, N, H, W, w_unscale, stream);
+}
+
+extern "C" int agrl_stem_split16_u8(const unsigned char* x, const float* table, int layout, const void* wh_packed, const void* wl_packed,
+                                    const float* bias, float* out, int N, int H, int W, float w_unscale, agrl_stream_t stream) {
+    FramesU8 u8;
+    if (frames_u8_args("agrl_stem_split16_u8", table, layout, H, W, &u8)) return 1;
+    return launch_stem_split16("agrl_stem_split16_u8", x, wh_packed, wl_packed, bias, out, N, H, W, w_unscale, stream, u8);
 }

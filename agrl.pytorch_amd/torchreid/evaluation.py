@@ -37,8 +37,9 @@ def pool_clips(features, num_clips, pool="avg"):
 def device_prefetch(batches, device):
     """Upload batch i+1 on a copy stream while batch i is being processed (the reference's test() uploads inside the
     loop, train_vidreid_xent_htri.py:460, and its loaders hand over pinned tensors, :222-247 ``pin_memory``): with pinned
-    sources the 100 MB of fp32 frames per 256-frame batch cross PCIe under the previous batch's forward. Yields the same
-    tuples with imgs / adj on ``device``; tensors already there pass through."""
+    sources the frames of a 256-frame batch -- 100 MB as fp32, 25 MB as the uint8 a decoder produces, which the models take as
+    they are -- cross PCIe under the previous batch's forward. The dtype is kept. Yields the same tuples with imgs / adj on
+    ``device``; tensors already there pass through."""
     if device.type != "cuda":
         for item in batches:
             yield item
@@ -76,6 +77,9 @@ def _claim(pending, main):
 def extract_features(model, batches, pool="avg", prefetch=True, local_only=False, sync_ranks=None):
     """``batches`` yields (imgs, pids, camids, adj) like the reference's loaders; imgs is (b,S,3,H,W) or, for the
     dense samplers, (b,n,S,3,H,W) with adj (b,n,V,V). Returns (features (N,D) on the model's device, pids, camids).
+    imgs is fp32 (normalised by the loader's transform_test) or uint8 -- channel-first as above or channel-last, (b,S,H,W,3) /
+    (b,n,S,H,W,3), straight from the decoder: a quarter of the PCIe bytes and no ToTensor / Normalize on the host; the model
+    normalises inside its stem kernel (model.pixel_mean / pixel_std), bit-identical to the fp32 route.
 
     Under an active process group (world > 1) the call is COLLECTIVE by default: every rank extracts its slice and then meets
     the others in ``match_and_rank``, so the non-finite flag is all-reduced (MAX) -- by every rank, whatever device its model
@@ -94,7 +98,7 @@ def extract_features(model, batches, pool="avg", prefetch=True, local_only=False
         clips = 1
         if imgs.dim() == 6:
             b, clips = imgs.shape[:2]
-            imgs = imgs.reshape((b * clips,) + tuple(imgs.shape[2:]))
+            imgs = imgs.reshape((b * clips,) + tuple(imgs.shape[2:]))   # whichever layout the trailing axes have
             adj = adj.reshape((b * clips,) + tuple(adj.shape[2:]))
         raw = model(imgs, adj)
         if raw.is_cuda:   # accumulated on the device, read once after the last batch: no per-batch synchronisation

@@ -63,17 +63,123 @@ def _dev(t):
     return torch.cuda.device(t.device)
 
 
-def stem(x_nchw, w_ohwi, bias, out_dtype):
-    """(N,3,H,W) fp32 NCHW -> (N,PH,PW,64) NHWC. vmgn.py:281-284."""
-    assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.size(1) == 3
-    x_nchw = x_nchw.contiguous()
-    N, _, H, W = x_nchw.shape
+PIXEL_MEAN = (0.485, 0.456, 0.406)   # the reference's transform_test: Normalize(mean, std) behind ToTensor
+PIXEL_STD = (0.229, 0.224, 0.225)    # (train_vidreid_xent_htri.py:214-217)
+
+
+def frame_table(mean=PIXEL_MEAN, std=PIXEL_STD):
+    """The canonical normalisation of a uint8 pixel value: (3, 256) fp32 on the CPU, T[c][u] = (float32(u) / 255 - mean[c]) / std[c] with
+    mean / std rounded to fp32 first and every operation a correctly rounded fp32 operation -- what ``F.to_tensor`` + ``F.normalize``
+    compute. (Multiplying by 1/255 instead of dividing is NOT the same: it differs in 322 of the 768 default entries.)"""
+    m = torch.tensor([float(v) for v in mean], dtype=torch.float32).view(3, 1)
+    s = torch.tensor([float(v) for v in std], dtype=torch.float32).view(3, 1)
+    if m.numel() != 3 or s.numel() != 3 or not bool((s != 0).all()):
+        raise ValueError("mean and std are three values each, std non-zero: got %r, %r" % (mean, std))
+    u = torch.arange(256, dtype=torch.float32).view(1, 256)
+    return u.div(255.0).sub(m).div(s)
+
+
+def frames_layout(shape):
+    """'nchw' for (..., 3, H, W) uint8 frames, 'nhwc' for (..., H, W, 3), decided by where the axis of size 3 sits (channel-first wins when
+    both fit); ValueError when neither does."""
+    if len(shape) >= 3 and shape[-3] == 3:
+        return 'nchw'
+    if len(shape) >= 3 and shape[-1] == 3:
+        return 'nhwc'
+    raise ValueError("uint8 frames are (..., 3, H, W) or (..., H, W, 3), got %s" % (tuple(shape),))
+
+
+def frames_normalize_reference(u8, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """uint8 frames (..., 3, H, W) or (..., H, W, 3) -> fp32 (..., 3, H, W) by indexing ``frame_table``: pure torch, any device. What
+    the CPU paths of the models use, and what the GPU kernels are compared with bit for bit."""
+    assert u8.dtype == torch.uint8
+    if frames_layout(u8.shape) == 'nhwc':
+        u8 = u8.movedim(-1, -3)
+    T = frame_table(mean, std).to(u8.device)
+    idx = u8.long()
+    return torch.stack([T[c][idx.select(-3, c)] for c in range(3)], dim=-3).contiguous()
+
+
+_FRAME_TABLES = {}
+
+
+def _device_frame_table(device, mean, std):
+    """The kernels' form of ``frame_table`` on ``device``: (3, 257) fp32, entry 256 of every row = 0 (the stems' zero padding is 0 in the
+    normalised domain). Cached per (device, mean, std): built -- one H2D copy -- the first time a triple is seen and never again, so a
+    forward issues no host synchronisation and stays capturable as a HIP graph once it has run eagerly."""
+    key = (str(device), tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    t = _FRAME_TABLES.get(key)
+    if t is None:
+        host = torch.zeros((3, 257), dtype=torch.float32)
+        host[:, :256] = frame_table(mean, std)
+        t = _FRAME_TABLES[key] = host.to(device).contiguous()
+    return t
+
+
+def _u8_frames(x, mean, std):
+    """(N,3,H,W) / (N,H,W,3) uint8 -> (contiguous x, device table, layout code, N, H, W)."""
+    assert x.dtype == torch.uint8 and x.dim() == 4
+    layout = frames_layout(x.shape)
+    x = x.contiguous()
+    N, H, W = (x.shape[0], x.shape[2], x.shape[3]) if layout == 'nchw' else (x.shape[0], x.shape[1], x.shape[2])
+    return x, _device_frame_table(x.device, mean, std), (_hip.FRAMES_NCHW if layout == 'nchw' else _hip.FRAMES_NHWC), N, H, W
+
+
+def frames_normalize(u8, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """uint8 frames (N,3,H,W) or (N,H,W,3) on the GPU -> fp32 NCHW (N,3,H,W), ``frame_table`` applied by agrl_frames_normalize_u8: for
+    the paths that do not fuse the normalisation into the stem (the native train step) and callers that want the tensor."""
+    x, table, layout, N, H, W = _u8_frames(u8, mean, std)
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=x.device)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * x.numel() + 4.0 * out.numel()}
+    with _dev(x):
+        call("agrl_frames_normalize_u8", ptr(x), ptr(table), layout, ptr(out), N, H, W, _stream(x))
+    return out
+
+
+def clip_frames(x):
+    """Validate uint8 clips as the models take them -- (B,S,3,H,W) or (B,S,H,W,3) -> (layout, B, S, H, W); ValueError otherwise."""
+    if x.dim() != 5:
+        raise ValueError("uint8 frames are (B,S,3,H,W) or (B,S,H,W,3), got %s" % (tuple(x.shape),))
+    layout = frames_layout(x.shape)
+    H, W = (x.shape[3], x.shape[4]) if layout == 'nchw' else (x.shape[2], x.shape[3])
+    return layout, x.shape[0], x.shape[1], H, W
+
+
+def clips_to_float(x, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """uint8 clips (B,S,3,H,W) / (B,S,H,W,3) -> fp32 (B,S,3,H,W), normalised: agrl_frames_normalize_u8 on the GPU, the table on the CPU.
+    The models call this in front of every path that does not fuse the normalisation into the stem (training, CPU)."""
+    _, B, S, H, W = clip_frames(x)
+    if x.is_cuda:
+        return frames_normalize(x.reshape((B * S,) + tuple(x.shape[2:])), mean, std).view(B, S, 3, H, W)
+    return frames_normalize_reference(x, mean, std)
+
+
+def _stem_frames(x, mean, std):
+    """The frames argument of the three stems: fp32 NCHW, or uint8 in either layout (normalised inside the kernel's input staging) ->
+    (x, N, H, W, bytes per input element, (table, layout) or None)."""
+    if x.dtype == torch.uint8:
+        x, table, layout, N, H, W = _u8_frames(x, mean, std)
+        return x, N, H, W, 1.0, (table, layout)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.size(1) == 3
+    x = x.contiguous()
+    return x, x.shape[0], x.shape[2], x.shape[3], 4.0, None
+
+
+def stem(x_nchw, w_ohwi, bias, out_dtype, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """(N,3,H,W) fp32 NCHW -- or uint8 frames, (N,3,H,W) / (N,H,W,3), normalised with ``frame_table(mean, std)`` while the kernel stages
+    them -> (N,PH,PW,64) NHWC. vmgn.py:281-284."""
+    x_nchw, N, H, W, _, u8 = _stem_frames(x_nchw, mean, std)
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     out = torch.empty((N, PH, PW, 64), dtype=out_dtype, device=x_nchw.device)
     with _dev(x_nchw):
-        call("agrl_stem_conv_bn_relu_maxpool", ptr(x_nchw), ptr(w_ohwi), ptr(bias), ptr(out), N, H, W,
-             dtype_code(out_dtype), _stream(x_nchw))
+        if u8 is not None:
+            call("agrl_stem_conv_bn_relu_maxpool_u8", ptr(x_nchw), ptr(u8[0]), u8[1], ptr(w_ohwi), ptr(bias), ptr(out), N, H, W,
+                 dtype_code(out_dtype), _stream(x_nchw))
+        else:
+            call("agrl_stem_conv_bn_relu_maxpool", ptr(x_nchw), ptr(w_ohwi), ptr(bias), ptr(out), N, H, W,
+                 dtype_code(out_dtype), _stream(x_nchw))
     return out
 
 
@@ -108,21 +214,24 @@ def pack_stem_weights_lp16(w_ohwi):
     return packed.contiguous()
 
 
-def stem_lp16(x_nchw, w_packed, bias):
-    """16-bit-MFMA stem: (N,3,H,W) fp32 NCHW -> (N,PH,PW,64) NHWC in the library's 16-bit type (LP_DTYPE). vmgn.py:281-284."""
-    assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.size(1) == 3
+def stem_lp16(x_nchw, w_packed, bias, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """16-bit-MFMA stem: (N,3,H,W) fp32 NCHW -- or uint8 frames in either layout, as in ``stem`` -> (N,PH,PW,64) NHWC in the library's
+    16-bit type (LP_DTYPE). vmgn.py:281-284."""
     assert w_packed.dtype == LP_DTYPE and tuple(w_packed.shape) == (64, 240)
-    x_nchw = x_nchw.contiguous()
-    N, _, H, W = x_nchw.shape
+    x_nchw, N, H, W, ebytes, u8 = _stem_frames(x_nchw, mean, std)
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     out = torch.empty((N, PH, PW, 64), dtype=LP_DTYPE, device=x_nchw.device)
     if _hip.PROFILE is not None:
-        _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": 4.0 * x_nchw.numel() + 2.0 * out.numel() + 2.0 * w_packed.numel(),
+        _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": ebytes * x_nchw.numel() + 2.0 * out.numel() + 2.0 * w_packed.numel(),
                             "conv": (7, 2, 3, 64, PH, PW)}
     with _dev(x_nchw):
-        call("agrl_stem_conv_bn_relu_maxpool_lp16", ptr(x_nchw), ptr(w_packed), ptr(bias), ptr(out), N, H, W,
-             _stream(x_nchw))
+        if u8 is not None:
+            call("agrl_stem_conv_bn_relu_maxpool_lp16_u8", ptr(x_nchw), ptr(u8[0]), u8[1], ptr(w_packed), ptr(bias), ptr(out), N, H, W,
+                 _stream(x_nchw))
+        else:
+            call("agrl_stem_conv_bn_relu_maxpool_lp16", ptr(x_nchw), ptr(w_packed), ptr(bias), ptr(out), N, H, W,
+                 _stream(x_nchw))
     return out
 
 
@@ -242,19 +351,22 @@ def pack_stem_weights_split16(w_ohwi):
     return out[0], out[1], ws.agrl_unscale
 
 
-def stem_split16(x_nchw, wh_packed, wl_packed, unscale, bias):
-    """Split-fp16 stem: (N,3,H,W) fp32 NCHW -> (N,PH,PW,64) fp32 NHWC (agrl_stem_split16). vmgn.py:281-284."""
-    assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.size(1) == 3
-    x_nchw = x_nchw.contiguous()
-    N, _, H, W = x_nchw.shape
+def stem_split16(x_nchw, wh_packed, wl_packed, unscale, bias, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """Split-fp16 stem: (N,3,H,W) fp32 NCHW -- or uint8 frames in either layout, as in ``stem`` -> (N,PH,PW,64) fp32 NHWC
+    (agrl_stem_split16). vmgn.py:281-284."""
+    x_nchw, N, H, W, ebytes, u8 = _stem_frames(x_nchw, mean, std)
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     out = torch.empty((N, PH, PW, 64), dtype=torch.float32, device=x_nchw.device)
     if _hip.PROFILE is not None:
-        _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": 4.0 * x_nchw.numel() + 4.0 * out.numel() + 4.0 * wh_packed.numel(),
+        _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": ebytes * x_nchw.numel() + 4.0 * out.numel() + 4.0 * wh_packed.numel(),
                             "conv": (7, 2, 3, 64, PH, PW)}
     with _dev(x_nchw):
-        call("agrl_stem_split16", ptr(x_nchw), ptr(wh_packed), ptr(wl_packed), ptr(bias), ptr(out), N, H, W, float(unscale), _stream(x_nchw))
+        if u8 is not None:
+            call("agrl_stem_split16_u8", ptr(x_nchw), ptr(u8[0]), u8[1], ptr(wh_packed), ptr(wl_packed), ptr(bias), ptr(out), N, H, W,
+                 float(unscale), _stream(x_nchw))
+        else:
+            call("agrl_stem_split16", ptr(x_nchw), ptr(wh_packed), ptr(wl_packed), ptr(bias), ptr(out), N, H, W, float(unscale), _stream(x_nchw))
     return out
 
 

@@ -19,7 +19,7 @@ import torch
 
 from torchreid import hip_ops as ops
 from torchreid import _hip
-from torchreid.models._vmgn_hip import (_PRECISIONS, run_stem, _fingerprint, _fold_bn1d, _fold_conv_bn, _pack_stage, _run_block, _run_trunk,
+from torchreid.models._vmgn_hip import (_PRECISIONS, eval_frames, run_stem, _fingerprint, _fold_bn1d, _fold_conv_bn, _pack_stage, _run_block, _run_trunk,
                                          check_packed_range)
 
 
@@ -71,11 +71,10 @@ def pack_weights(model, device, precision):
 
 
 def hip_forward_ganet(model, x, adj, stages=None):
-    """Eval forward of ``ganet`` on the GPU: (B,S,3,H,W) fp32, (B,V,V) fp32 -> (B, (num_gb + 1) * 2048) fp32."""
+    """Eval forward of ``ganet`` on the GPU: (B,S,3,H,W) fp32 (or uint8 frames, see _vmgn_hip.hip_forward), (B,V,V) fp32 ->
+    (B, (num_gb + 1) * 2048) fp32."""
     _hip.lib()
-    if x.dtype != torch.float32:
-        raise TypeError('frames must be float32, got {}'.format(x.dtype))
-    B, S, Cc, H, W = x.shape
+    frames, B, S, norm = eval_frames(model, x)
     P = model.total_split
     V = S * P
     if tuple(adj.shape) != (B, V, V):
@@ -84,8 +83,7 @@ def hip_forward_ganet(model, x, adj, stages=None):
     lp = pack['dtype'] == ops.LP_DTYPE
     splits = list(model.total_split_list)
     with torch.no_grad(), ops.f32_split(model.hip_precision == 'bf16x3'):
-        frames = x.reshape(B * S, Cc, H, W)
-        a = run_stem(frames, pack)
+        a = run_stem(frames, pack, norm)
         a = _run_trunk(a, pack['trunk'])
         for blk in pack['l4']:
             a = _run_block(a, blk)

@@ -2,7 +2,7 @@
 -> GSTA.forward, vmgn.py:292-321) through the C-ABI of libagrl_hip.so.
 
 Data layout in HBM
-    frames        fp32 NCHW (B*S,3,H,W)  as handed over by the driver (read once by the stem kernel)
+    frames        fp32 NCHW (B*S,3,H,W)  as handed over by the driver (read once by the stem kernel); or uint8, (B*S,3,H,W) / (B*S,H,W,3)
     activations   NHWC (B*S, h, w, C) in the compute dtype (fp32 parity mode / bf16 throughput mode)
     conv weights  OHWI (Cout, R, S, Cin), eval BatchNorm folded in, compute dtype; bias fp32
     part nodes    fp32 (B, V = S*P, 2048)
@@ -365,19 +365,42 @@ def _run_block(x, blk, pool=None):
     return ops.conv_bn_act(y, blk['c3'][0], blk['c3'][1], 1, 0, True, residual=shortcut)
 
 
-def run_stem(frames, pack):
+def run_stem(frames, pack, norm=None):
     """conv1 / bn1 / relu / maxpool (vmgn.py:281-284) in the pack's arithmetic: the 16-bit MFMA stem, the split-fp16 one of the conforming
-    mode, or the exact-fp32 one."""
+    mode, or the exact-fp32 one. ``frames``: fp32 NCHW, or uint8 (F,3,H,W) / (F,H,W,3) -- then every stem normalises inside its input
+    staging with ``norm`` = (pixel_mean, pixel_std) (None: the ImageNet defaults) and no fp32 frame tensor exists."""
+    mean, std = norm if norm is not None else (ops.PIXEL_MEAN, ops.PIXEL_STD)
     if pack['stem_lp'] is not None:
-        return ops.stem_lp16(frames, pack['stem_lp'], pack['stem'][1])
+        return ops.stem_lp16(frames, pack['stem_lp'], pack['stem'][1], mean, std)
     if pack.get('stem_s16') is not None:
-        return ops.stem_split16(frames, pack['stem_s16'][0], pack['stem_s16'][1], pack['stem_s16'][2], pack['stem'][1])
-    return ops.stem(frames, pack['stem'][0], pack['stem'][1], pack['dtype'])
+        return ops.stem_split16(frames, pack['stem_s16'][0], pack['stem_s16'][1], pack['stem_s16'][2], pack['stem'][1], mean, std)
+    return ops.stem(frames, pack['stem'][0], pack['stem'][1], pack['dtype'], mean, std)
 
 
-def hip_featuremaps(frames, pack):
-    """(F,3,H,W) fp32 NCHW -> x4_1, x4_2 NHWC (F,h,w,2048). reference vmgn.py:280-290."""
-    a = run_stem(frames, pack)
+def eval_frames(model, x):
+    """The frames argument of the three eval forwards: (B,S,3,H,W) fp32, or uint8 (B,S,3,H,W) / (B,S,H,W,3) as a decoder produces them
+    -> (frames (B*S, ...) in x's dtype and layout, B, S, norm for run_stem). Any other dtype is a TypeError, a uint8 tensor in neither
+    layout a ValueError."""
+    if x.dtype == torch.uint8:
+        _, B, S, _, _ = ops.clip_frames(x)
+        norm = (getattr(model, 'pixel_mean', ops.PIXEL_MEAN), getattr(model, 'pixel_std', ops.PIXEL_STD))
+        return x.reshape((B * S,) + tuple(x.shape[2:])), B, S, norm
+    if x.dtype != torch.float32:
+        raise TypeError('frames must be float32, got {}'.format(x.dtype))
+    B, S, Cc, H, W = x.shape
+    return x.reshape(B * S, Cc, H, W), B, S, None
+
+
+def _frame_size(frames):
+    """(H, W) of fp32 NCHW or uint8 NCHW / NHWC frames."""
+    if frames.dtype == torch.uint8 and ops.frames_layout(frames.shape) == 'nhwc':
+        return frames.shape[1], frames.shape[2]
+    return frames.shape[2], frames.shape[3]
+
+
+def hip_featuremaps(frames, pack, norm=None):
+    """(F,3,H,W) fp32 NCHW (or uint8 frames, see run_stem) -> x4_1, x4_2 NHWC (F,h,w,2048). reference vmgn.py:280-290."""
+    a = run_stem(frames, pack, norm)
     a = _run_trunk(a, pack['trunk'])
     x4_1 = a
     for blk in pack['l4_1']:
@@ -388,7 +411,7 @@ def hip_featuremaps(frames, pack):
     return x4_1, x4_2
 
 
-def hip_features_pooled(frames, pack, splits):
+def hip_features_pooled(frames, pack, splits, norm=None):
     """Conv stages with the global / part pooling fused into the last conv of each layer4 branch, on 16-bit tensors or -- in the
     conforming mode with planes -- on split-fp16 planes behind layer 3's first block (16x8 maps): -> gsum (F,C) per-frame sums,
     nodes (F,P,C) fp32. None when the fusion does not apply."""
@@ -397,13 +420,13 @@ def hip_features_pooled(frames, pack, splits):
         return None
     # applicability is decided from the input size BEFORE anything is launched (a late bail-out would make the caller
     # recompute stem + trunk): the fused epilogue needs 16 x 8 = 128-pixel layer-4 maps, i.e. frames of 256 x 128
-    H, W = frames.shape[2], frames.shape[3]
+    H, W = _frame_size(frames)
     h4, w4 = H, W
     for _ in range(4):   # stem conv /2, maxpool /2, layer2 /2, layer3 /2 (kernel 7 pad 3 / kernel 3 pad 1: ceil halving)
         h4, w4 = (h4 + 1) // 2, (w4 + 1) // 2
     if (h4, w4) != (16, 8):
         return None
-    a = run_stem(frames, pack)
+    a = run_stem(frames, pack, norm)
     if first is None:
         run_block = _run_block
         a = _run_trunk(a, pack['trunk'])
@@ -457,13 +480,12 @@ def hip_graph_layers(nodes, nodes_lp, adj, pack, stages=None, commute=True):
 
 
 def hip_forward(model, x, adj, return_feats=False, stages=None):
-    """Eval forward on the GPU: (B,S,3,H,W) fp32, (B,V,V) fp32 -> (B,4096) fp32. ``stages``: an optional dict that
+    """Eval forward on the GPU: (B,S,3,H,W) fp32 -- or uint8 frames, (B,S,3,H,W) / (B,S,H,W,3), normalised with model.pixel_mean /
+    pixel_std inside the stem kernel -- and (B,V,V) fp32 -> (B,4096) fp32. ``stages``: an optional dict that
     receives the intermediate tensors of the path (per-frame sums of x4_1, part nodes, graphs, graph output, pre-BN
     features) for the stage-by-stage parity tests."""
     _hip.lib()  # fail loudly before touching anything if the extension is missing
-    if x.dtype != torch.float32:
-        raise TypeError('frames must be float32, got {}'.format(x.dtype))
-    B, S, Cc, H, W = x.shape
+    frames, B, S, norm = eval_frames(model, x)
     P = model.total_split
     V = S * P
     packed_adj = ops.adjacency_is_packed(adj)   # int32 (B, V, ceil(V/32)): the bit-packed graph (hip_ops.adjacency_pack*)
@@ -473,13 +495,12 @@ def hip_forward(model, x, adj, return_feats=False, stages=None):
     pack = pack_weights(model, x.device, model.hip_precision)
     lp = pack['dtype'] == ops.LP_DTYPE
     with torch.no_grad(), ops.f32_split(model.hip_precision == 'bf16x3'):
-        frames = x.reshape(B * S, Cc, H, W)
-        fused = hip_features_pooled(frames, pack, model.total_split_list)
+        fused = hip_features_pooled(frames, pack, model.total_split_list, norm)
         if fused is not None:
             gsum, nodes = fused
             hw = 128
         else:
-            x4_1, x4_2 = hip_featuremaps(frames, pack)
+            x4_1, x4_2 = hip_featuremaps(frames, pack, norm)
             hw = x4_1.shape[1] * x4_1.shape[2]
             gsum, nodes, _ = ops.part_pool(x4_1, x4_2, model.total_split_list, want_lp=False)
             del x4_1, x4_2
@@ -508,13 +529,11 @@ def hip_forward(model, x, adj, return_feats=False, stages=None):
 
 
 def hip_forward_gsta(model, x, adj):
-    """Eval forward of the single-branch ``gsta`` on the GPU: (B,S,3,H,W) fp32, (B,V,V) fp32 -> (B,2048) fp32.
+    """Eval forward of the single-branch ``gsta`` on the GPU: (B,S,3,H,W) fp32 (or uint8 frames, see hip_forward), (B,V,V) fp32 -> (B,2048) fp32.
     reference gsta.py:273-298. Same kernels as vmgn; the attention tail kernel writes cat(BN(global), BN(attention)) and
     only its second half exists for this model (the global half is fed zeros)."""
     _hip.lib()
-    if x.dtype != torch.float32:
-        raise TypeError('frames must be float32, got {}'.format(x.dtype))
-    B, S, Cc, H, W = x.shape
+    frames, B, S, norm = eval_frames(model, x)
     P = model.total_split
     V = S * P
     if tuple(adj.shape) != (B, V, V):
@@ -523,8 +542,7 @@ def hip_forward_gsta(model, x, adj):
     lp = pack['dtype'] == ops.LP_DTYPE
     splits = list(model.total_split_list)
     with torch.no_grad(), ops.f32_split(model.hip_precision == 'bf16x3'):
-        frames = x.reshape(B * S, Cc, H, W)
-        a = run_stem(frames, pack)
+        a = run_stem(frames, pack, norm)
         a = _run_trunk(a, pack['trunk'])
         if lp and a.shape[1] * a.shape[2] == 128 and pack['l4'][0]['stride'] == 1:
             for blk in pack['l4'][:-1]:

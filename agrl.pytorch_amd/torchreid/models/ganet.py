@@ -157,6 +157,10 @@ class GANet(nn.Module):
         _ops.check_precision(self.hip_precision)
         self.hip_static_weights = False
         self._hip_packs = {}
+        # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
+        # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
+        self.pixel_mean = (0.485, 0.456, 0.406)
+        self.pixel_std = (0.229, 0.224, 0.225)
 
     def _init_params(self):
         """reference ganet.py:352-366"""
@@ -185,6 +189,9 @@ class GANet(nn.Module):
         if x.is_cuda and not self.training:
             from torchreid.models._ganet_hip import hip_forward_ganet
             return hip_forward_ganet(self, x, adj)
+        if x.dtype == torch.uint8:   # every path below reads fp32 frames: normalise first (hip_ops.clips_to_float), then exactly that path
+            from torchreid import hip_ops as _ops
+            x = _ops.clips_to_float(x, self.pixel_mean, self.pixel_std)
         B, S, C, H, W = x.size()
         fm = self.featuremaps(x.view(B * S, C, H, W))
         _, c, h, w = fm.shape

@@ -64,6 +64,10 @@ class GSTASingle(nn.Module):
         self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode forward + backward on the HIP kernels
         self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')
         self._hip_packs = {}
+        # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
+        # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
+        self.pixel_mean = (0.485, 0.456, 0.406)
+        self.pixel_std = (0.229, 0.224, 0.225)
 
     def _init_params(self):
         """reference gsta.py:240-256"""
@@ -88,6 +92,9 @@ class GSTASingle(nn.Module):
         if x.is_cuda and not self.training:
             from torchreid.models._vmgn_hip import hip_forward_gsta
             return hip_forward_gsta(self, x, adj)
+        if x.dtype == torch.uint8:   # every path below reads fp32 frames: normalise first (hip_ops.clips_to_float), then exactly that path
+            from torchreid import hip_ops as _ops
+            x = _ops.clips_to_float(x, self.pixel_mean, self.pixel_std)
         if x.is_cuda and self.training and self.hip_train:
             if x.dtype != torch.float32:
                 raise TypeError('the native train step takes float32 frames, got {}; set model.hip_train = False for the '

@@ -182,6 +182,10 @@ class GSTA(nn.Module):
         self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')   # 'fp32' exact | 'bf16x3' split-bf16 MFMA
         self.hip_train_tail = os.environ.get('AGRL_HIP_TRAIN_TAIL', '1') != '0'         # tail of the train forward native as well
         self._hip_packs = {}
+        # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
+        # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
+        self.pixel_mean = (0.485, 0.456, 0.406)
+        self.pixel_std = (0.229, 0.224, 0.225)
 
     # ------------------------------------------------------------------ stock-torch path (CPU / train)
     def _attention_op(self, feat):
@@ -206,6 +210,9 @@ class GSTA(nn.Module):
             from torchreid.models._vmgn_hip import hip_forward
             return hip_forward(self, x, adj)
 
+        if x.dtype == torch.uint8:   # every path below reads fp32 frames: normalise first (hip_ops.clips_to_float), then exactly that path
+            from torchreid import hip_ops as _ops
+            x = _ops.clips_to_float(x, self.pixel_mean, self.pixel_std)
         B, S, C, H, W = x.size()
         if x.is_cuda and self.training and self.hip_train and x.dtype != torch.float32:
             raise TypeError('the native train step takes float32 frames (the reference trains in fp32), got {}; '

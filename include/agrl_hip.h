@@ -86,6 +86,31 @@ int agrl_stem_conv_bn_relu_maxpool_lp16(const float* x, const void* w_packed, co
 int agrl_stem_split16(const float* x, const void* wh_packed, const void* wl_packed, const float* bias, float* out, int N, int H,
                       int W, float w_unscale, agrl_stream_t stream);
 
+/* ---- uint8 frames ------------------------------------------------------------------------------
+ * Frames as a decoder produces them: one byte per channel value, either channel-first (N,3,H,W) = AGRL_FRAMES_NCHW or channel-last
+ * (N,H,W,3) = AGRL_FRAMES_NHWC (what PIL and the video decoders hand over). The reference normalises on the host
+ * (transform_test = ToTensor + Normalize, train_vidreid_xent_htri.py:214-217); here the caller passes that arithmetic as a device
+ * TABLE, fp32 (3, 257): table[c][u] = (float(u) / 255 - mean[c]) / std[c] with every operation a correctly rounded fp32 operation
+ * (mean / std rounded to fp32 first), u = 0..255, and table[c][256] = 0 -- the entry the stem kernels give their zero padding, which is
+ * 0 in the normalised domain. The kernels only look values up, so a uint8 launch is bit-identical to the fp32 launch on the tensor
+ * built from the same table, and no fp32 frame tensor exists in HBM.
+ *
+ * The three stems below are agrl_stem_conv_bn_relu_maxpool / _lp16 / agrl_stem_split16 with (x, table, layout) in place of the fp32 x;
+ * every other argument, the output and the arithmetic are theirs. */
+#define AGRL_FRAMES_NCHW 0
+#define AGRL_FRAMES_NHWC 1
+int agrl_stem_conv_bn_relu_maxpool_u8(const unsigned char* x, const float* table, int layout, const float* w, const float* bias,
+                                      void* out, int N, int H, int W, int out_dtype, agrl_stream_t stream);
+int agrl_stem_conv_bn_relu_maxpool_lp16_u8(const unsigned char* x, const float* table, int layout, const void* w_packed,
+                                           const float* bias, void* out, int N, int H, int W, agrl_stream_t stream);
+int agrl_stem_split16_u8(const unsigned char* x, const float* table, int layout, const void* wh_packed, const void* wl_packed,
+                         const float* bias, float* out, int N, int H, int W, float w_unscale, agrl_stream_t stream);
+
+/* uint8 frames (either layout) -> out fp32 NCHW (N,3,H,W) = table[c][x]: for the paths that do not fuse the normalisation (the native
+ * train step, whose stem reads fp32 through agrl_im2col_rows) and any caller that wants the tensor. */
+int agrl_frames_normalize_u8(const unsigned char* x, const float* table, int layout, float* out, int N, int H, int W,
+                             agrl_stream_t stream);
+
 /* Implicit-GEMM convolution (1x1 or 3x3, stride 1|2) + folded BN + optional residual + optional
  * ReLU, NHWC in / NHWC out. One call == one (conv, bn[, +residual][, relu]) group of
  * Bottleneck.forward, torchreid/models/vmgn.py:45-65 (and the downsample branch :58-59).
