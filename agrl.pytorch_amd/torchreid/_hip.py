@@ -144,6 +144,9 @@ SIGNATURES = {
     "agrl_maxpool3x3s2": [_p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_maxpool3x3s2_backward": [_p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_diag_read_stream": [_p, C.c_size_t, _p, _i, _p],
+    "agrl_optim_geometry": [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "agrl_adam_step": [_p, _i, _p, _i] + [_f] * 7 + [_i, _i, _p],
+    "agrl_sgd_step": [_p, _i, _p, _i, _f, _f, _f, _i, _i, _i, _i, _p],
 }
 
 _lock = threading.Lock()

@@ -1586,3 +1586,33 @@ def xent_label_smooth(logits, targets, eps):
     with _dev(logits):
         call("agrl_xent_label_smooth", ptr(logits), ptr(targets), n, K, float(eps), ptr(loss), ptr(dl), ptr(rows), _stream(logits))
     return loss, dl
+
+
+# ---- optimiser update (include/agrl_hip.h, "optimiser update of the train step"; host side: torchreid/hip_optim.py) --------
+def optim_geometry():
+    """-> (elements per chunk, workgroups at most, int64 words per tensor descriptor): the library's constants."""
+    chunk, grid, words = C.c_int(0), C.c_int(0), C.c_int(0)
+    _hip._check("agrl_optim_geometry", _hip.lib().agrl_optim_geometry(C.byref(chunk), C.byref(grid), C.byref(words)))
+    return chunk.value, grid.value, words.value
+
+
+def _optim_tables(tensors, chunks):
+    assert tensors.dtype == torch.int64 and tensors.dim() == 2 and chunks.dtype == torch.int32 and chunks.dim() == 2 and chunks.size(1) == 2
+    assert tensors.device == chunks.device
+    return ptr(tensors), tensors.size(0), ptr(chunks), chunks.size(0)
+
+
+def adam_step(tensors, chunks, weight_decay, one_minus_beta1, beta2, one_minus_beta2, step_size, inv_sqrt_bc2, eps, amsgrad, zero_grad):
+    """One multi-tensor Adam / AMSGrad update in place. tensors: int64 (n, words) descriptor table, chunks: int32 (n_chunks, 2), both
+    on the parameters' device; the seven constants are fp32 values formed in double by the caller. optimizers.py:8-11."""
+    with _dev(tensors):
+        call("agrl_adam_step", *_optim_tables(tensors, chunks), float(weight_decay), float(one_minus_beta1), float(beta2),
+             float(one_minus_beta2), float(step_size), float(inv_sqrt_bc2), float(eps), 1 if amsgrad else 0, 1 if zero_grad else 0,
+             _stream(tensors))
+
+
+def sgd_step(tensors, chunks, weight_decay, momentum, lr, has_momentum, first_step, nesterov, zero_grad):
+    """One multi-tensor SGD update in place (momentum / Nesterov momentum, dampening 0). optimizers.py:12-15."""
+    with _dev(tensors):
+        call("agrl_sgd_step", *_optim_tables(tensors, chunks), float(weight_decay), float(momentum), float(lr), 1 if has_momentum else 0,
+             1 if first_step else 0, 1 if nesterov else 0, 1 if zero_grad else 0, _stream(tensors))

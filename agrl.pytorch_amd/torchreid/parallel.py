@@ -179,16 +179,26 @@ class GradientBuckets(object):
         self._pending = [0] * len(self.buckets)
         self._handles = []
         self._hit = set()
+        self._clean = False
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in self.params]
         self.zero_grad()
 
     def zero_grad(self):
-        """Instead of optimizer.zero_grad(): keeps the .grad views alive (set_to_none would detach them from the buffers)."""
+        """Instead of optimizer.zero_grad(): keeps the .grad views alive (set_to_none would detach them from the buffers). After
+        mark_clean() the buffers are known to be zero already: only the counters are re-armed."""
         for i, (flat, group) in enumerate(self.buckets):
-            flat.zero_()
+            if not self._clean:
+                flat.zero_()
             self._pending[i] = len(group)
+        self._clean = False
         self._handles = []
         self._hit = set()
+
+    def mark_clean(self):
+        """The caller's word that every flat buffer is entirely zero -- after a native optimiser step with ``zero_grads=True`` inside
+        only_touched(): that step stored +0.0 over every gradient it consumed, and the slices of the parameters it skipped were
+        never written since the last fill. The next zero_grad() then skips its memset pass (188 MB for vmgn), once."""
+        self._clean = True
 
     def _on_grad(self, p):
         i = self._bucket_of[p]
@@ -264,7 +274,8 @@ def train_step(model, imgs, adj, pids, criterion_xent, criterion_htri, optimizer
     over the ranks, losses and the batch-hard mining (native kernel) on the GLOBAL batch, backward, gradient all-reduce,
     optimizer step. Returns the (global) loss values. With one rank it is exactly the reference's step.
     ``buckets``: a GradientBuckets over model.parameters() -> the all-reduces overlap backward; without it the gradients
-    are reduced in flat buckets after backward."""
+    are reduced in flat buckets after backward. With ``buckets`` and a native optimiser (torchreid.hip_optim) the step also
+    zero-fills the gradients, and the buckets' own fill before the next backward is skipped."""
     from torchreid.losses import DeepSupervision
     model.train()
     outputs, features = model(imgs, adj)
@@ -278,8 +289,15 @@ def train_step(model, imgs, adj, pids, criterion_xent, criterion_htri, optimizer
         buckets.zero_grad()
         loss.backward()
         buckets.finish()
-        with buckets.only_touched():
-            optimizer.step()
+        from torchreid.hip_optim import NativeStepMixin
+        if isinstance(optimizer, NativeStepMixin):
+            # the native step zero-fills the gradients it consumes in its own pass: no memset before the next backward
+            with buckets.only_touched():
+                optimizer.step(zero_grads=True)
+            buckets.mark_clean()
+        else:
+            with buckets.only_touched():
+                optimizer.step()
     else:
         optimizer.zero_grad()
         loss.backward()

@@ -700,6 +700,32 @@ int agrl_diag_read_stream(const void* src, size_t bytes, float* sink, int workgr
 int agrl_triplet_loss(const float* x, const int32_t* pids, int n, int d, float margin, int soft, float* loss, float* grad,
                       float* dist_ap, float* dist_an, int32_t* idx_ap, int32_t* idx_an, float* coeff, agrl_stream_t stream);
 
+/* ---- optimiser update of the train step (optimizer.step(), train_vidreid_xent_htri.py:411-413; optimizers.py:7-23) -----------
+ * One launch updates many fp32 tensors in place. ``tensors``: device array of n_tensors descriptors of descriptor_words int64
+ * words each, {param, grad, state0, state1, state2, numel, vec, 0}: Adam state0 = exp_avg, state1 = exp_avg_sq, state2 =
+ * max_exp_avg_sq (AMSGrad only, else 0); SGD state0 = momentum_buffer (0 without momentum). vec != 0 promises that the param,
+ * grad and state pointers of that tensor are all 16-byte aligned (16-byte accesses; otherwise dwords; numel is arbitrary either
+ * way). ``chunks``: device array of n_chunks int32 pairs {tensor, chunk index inside the tensor}; chunk c of a tensor covers its
+ * elements [c * chunk_elems, min(numel, (c + 1) * chunk_elems)), and every element of every tensor must be in exactly one chunk.
+ * Nothing is allocated, nothing synchronises; the kernel runs on ``stream``. zero_grad != 0: +0.0 is stored to every gradient
+ * element after it has been consumed. The geometry getter reports the library's constants (host memory). */
+int agrl_optim_geometry(int* chunk_elems, int* max_workgroups, int* descriptor_words);
+
+/* Adam / AMSGrad (torch.optim.Adam, L2 weight decay), per element in this order, IEEE division and square root:
+ *   gd = g + weight_decay p;  m += one_minus_beta1 (gd - m);  v = beta2 v + one_minus_beta2 gd^2;
+ *   amsgrad: vmax = max(vmax, v), used for v below;  p -= step_size m / (sqrt(v) inv_sqrt_bc2 + eps)
+ * with step_size = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) for the step count t of EVERY tensor of the
+ * launch; the caller forms all constants in double and rounds each once to fp32. */
+int agrl_adam_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay,
+                   float one_minus_beta1, float beta2, float one_minus_beta2, float step_size, float inv_sqrt_bc2, float eps,
+                   int amsgrad, int zero_grad, agrl_stream_t stream);
+
+/* SGD (torch.optim.SGD, dampening 0):  gd = g + weight_decay p;  has_momentum: buf = gd when first_step, else momentum buf + gd;
+ * d = gd + momentum buf (nesterov) or buf;  without momentum d = gd;  p -= lr d. first_step holds for every tensor of the launch
+ * (their buffers are written, not read). */
+int agrl_sgd_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay, float momentum,
+                  float lr, int has_momentum, int first_step, int nesterov, int zero_grad, agrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
