@@ -1,6 +1,7 @@
 // Shared device/host helpers for libagrl_hip.so (gfx950 only: 64-lane wavefronts are assumed).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -44,6 +45,22 @@ void agrl_set_error(const char* fmt, ...);
             return 2;                                                             \
         }                                                                         \
     } while (0)
+
+// A positive finite power of two -- what every un-scaling factor of the split-fp16 entry points must be for the un-scaling to be
+// exact. NaN, zero, negative, infinite and non-power-of-two values are refused.
+static inline bool agrl_is_pow2(float v) {
+    int e = 0;
+    return v > 0.f && v <= 3.4e38f && frexpf(v, &e) == 0.5f;
+}
+#define AGRL_CHECK_POW2(value, who, name) \
+    AGRL_CHECK_ARG(agrl_is_pow2(value), "%s: %s=%g is not a positive finite power of two", who, name, (double)(value))
+
+// compute units of the current device (256 when the query fails); cached per device ordinal, no lock. Library-internal: not exported
+__attribute__((visibility("hidden"))) int agrl_cu_count();
+
+// LDS / global address-space pointers, as __builtin_amdgcn_global_load_lds takes them
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) const void gbl_void_t;
 
 // ---- 16-bit <-> f32 (round-to-nearest-even, NaN preserved; matches torch .to(float16) / .to(bfloat16)) -------------
 __host__ __device__ inline float lp16_to_f32(lp16_t v) {

@@ -15,6 +15,23 @@ extern "C" const char* agrl_last_error(void) { return g_err; }
 
 extern "C" int agrl_lp16_is_f16(void) { return kLpF16 ? 1 : 0; }
 
+// ---- compute units of the current device. One slot per device ordinal, 0 = not asked yet; threads that race on the first call
+// store the same value, so a relaxed atomic is all the synchronisation there is. hipGetDevice reads a thread-local, no device.
+#include <atomic>
+
+int agrl_cu_count() {
+    constexpr int kMaxDev = 64;
+    static std::atomic<int> cache[kMaxDev];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    const bool slot = dev >= 0 && dev < kMaxDev;
+    int n = slot ? cache[dev].load(std::memory_order_relaxed) : 0;
+    if (n > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    if (slot) cache[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
 // ---- tuning switches (agrl_common.h) ----------------------------------------------------------------------------------
 #include <stdlib.h>
 

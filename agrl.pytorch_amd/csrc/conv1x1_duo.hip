@@ -962,11 +962,7 @@ static int duo_split16_common(DuoParams& p, const void* x, const void* packed, c
     AGRL_CHECK_ARG(x && packed && bias, "%s: null pointer", who);
     AGRL_CHECK_ARG(M > 0 && K3 > 0 && K3 % 384 == 0 && Cout > 0 && Cout % 256 == 0, "%s: needs K3 %% 384 == 0 (3 planes of whole 128-channel slabs) and Cout %% 256 == 0; got M=%d K3=%d Cout=%d", who, M, K3, Cout);
     AGRL_CHECK_ARG((size_t)M * (size_t)(K3 > 3 * Cout ? K3 : 3 * Cout) * 2 < (1ull << 32), "%s: maps beyond 4 GB are not addressed", who);
-    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale <= 3.4e38f, "%s: w_unscale must be a positive finite power of two", who);
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "%s: w_unscale=%g is not a power of two", who, (double)w_unscale);
-    }
+    AGRL_CHECK_POW2(w_unscale, who, "w_unscale");
     p.x = reinterpret_cast<const unsigned char*>(x);
     p.wpk = reinterpret_cast<const unsigned char*>(packed);
     p.bias = bias;
@@ -1083,10 +1079,7 @@ extern "C" int agrl_split16_weight_planes(const float* x, void* out, long long r
     AGRL_CHECK_ARG(agrl_lp16_is_f16(), "agrl_split16_weight_planes: the split planes are fp16 (load libagrl_hip.so, not the bf16 build)");
     AGRL_CHECK_ARG(x && out && rows > 0 && C > 0 && C % 4 == 0, "agrl_split16_weight_planes: needs C %% 4 == 0 (got rows=%lld C=%d)", rows, C);
     AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "agrl_split16_weight_planes: pointers must be 16-byte aligned");
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(scale > 0.f && scale <= 3.4e38f && frexpf(scale, &e) == 0.5f, "agrl_split16_weight_planes: scale=%g is not a positive power of two", (double)scale);
-    }
+    AGRL_CHECK_POW2(scale, "agrl_split16_weight_planes", "scale");
     const long long groups = rows * (C / 4);
     const int grid = (int)((groups + 255) / 256 < 8192 ? (groups + 255) / 256 : 8192);
     hipLaunchKernelGGL(split16_weight_planes_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x),

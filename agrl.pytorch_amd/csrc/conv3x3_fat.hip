@@ -574,11 +574,7 @@ static int fat3_launch(const void* x, const void* packed, const float* bias, voi
     // two pixel blocks per workgroup where that still gives every CU a workgroup, else one
     // one-block launches that would put ONE workgroup on a CU (layer 3): two half-width workgroups per block instead
     // (AGRL_CONV3X3_HALF = 0 / 1 forces it off / on; AGRL_CONV3X3_HALF_STAGGER: start delay of the second resident round, clocks)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    const int cus = agrl_cu_count();
     const int want_half = agrl_opts().conv3x3_half;
     if (agrl_opt_set(want_half) ? want_half != 0 : ((p.nblocks / 2) * nNt < 224 && p.nblocks * nNt <= cus && p.nblocks * nNt >= cus / 2)) {
         const int stagger = agrl_opt_set(agrl_opts().conv3x3_half_stagger) ? agrl_opts().conv3x3_half_stagger : 0;

@@ -182,20 +182,11 @@ __global__ __launch_bounds__(512) void graph_linear_kernel(const GraphGemmParams
 
 }  // namespace
 
-static int graph_gemm_cus() {
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
-    return n_cu;
-}
-
 // One round of tiles only: with more tiles than CUs the generic kernel's two workgroups per CU (one's epilogue under the
 // other's k loop) are as fast or faster (measured at 64 / 256 tracklets: 47.9 / 187 us against 47.9 / 200 us for a
 // two-slot form of this kernel), at one round this kernel is (27.9 against 31.7 us at 32 tracklets).
 bool graph_gemm_applicable(int M, int K, int Nout) {
-    return M > 0 && (K % 64) == 0 && K >= 64 && (Nout % GBN) == 0 && ((M + GBM - 1) / GBM) * (Nout / GBN) <= graph_gemm_cus();
+    return M > 0 && (K % 64) == 0 && K >= 64 && (Nout % GBN) == 0 && ((M + GBM - 1) / GBM) * (Nout / GBN) <= agrl_cu_count();
 }
 
 int launch_graph_gemm(const void* p_op, const void* w, const float* f, const float* bn_scale, const float* bn_shift, float keep,

@@ -1190,11 +1190,7 @@ extern "C" int agrl_conv2d_bn_act_split16(const void* x, const void* w_scaled, c
     AGRL_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && pad >= 0,
                    "agrl_conv2d_bn_act_split16: bad shape");
     AGRL_CHECK_ARG(Cin % 32 == 0, "agrl_conv2d_bn_act_split16: Cin=%d must be a multiple of 32 (the pre-split weight k-tile)", Cin);
-    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale == w_unscale && w_unscale <= 3.4e38f, "agrl_conv2d_bn_act_split16: w_unscale must be a positive finite power of two");
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "agrl_conv2d_bn_act_split16: w_unscale=%g is not a power of two (the un-scaling must be exact)", (double)w_unscale);
-    }
+    AGRL_CHECK_POW2(w_unscale, "agrl_conv2d_bn_act_split16", "w_unscale");
     IgemmParams p{};
     p.x2 = nullptr; p.K1 = 0; p.stats = nullptr;
     p.x = x; p.w = w_scaled; p.colv = bias; p.rowv = nullptr; p.res = residual; p.out = out;
@@ -1223,11 +1219,7 @@ extern "C" int agrl_conv1x1_dual_split16(const void* x, const void* x2, const vo
     AGRL_CHECK_ARG(N > 0 && H > 0 && W > 0 && stride >= 1 && K1 > 0 && K2 > 0 && Cout > 0, "agrl_conv1x1_dual_split16: bad shape");
     AGRL_CHECK_ARG(K1 % 32 == 0 && K2 % 32 == 0, "agrl_conv1x1_dual_split16: K1 and K2 must be multiples of 32 (got %d, %d)", K1, K2);
     AGRL_CHECK_ARG((((uintptr_t)x2) & 15) == 0, "agrl_conv1x1_dual_split16: x2 must be 16-byte aligned");
-    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale <= 3.4e38f, "agrl_conv1x1_dual_split16: w_unscale must be a positive finite power of two");
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "agrl_conv1x1_dual_split16: w_unscale=%g is not a power of two", (double)w_unscale);
-    }
+    AGRL_CHECK_POW2(w_unscale, "agrl_conv1x1_dual_split16", "w_unscale");
     IgemmParams p{};
     p.x = x; p.x2 = x2; p.K1 = K1; p.stats = nullptr; p.a_pre = x2_presplit ? 2 : 0; p.out_planes = out_planes;
     p.w = w_scaled; p.colv = bias; p.rowv = nullptr; p.res = nullptr; p.out = out;
@@ -1491,11 +1483,8 @@ extern "C" int agrl_distmat(const void* q, const void* g, const float* qn, const
 extern "C" int agrl_distmat_split16(const void* q3, const void* g3, const float* qn, const float* gn, float* dist, int m, int n, int D3,
                                     int ldd, int metric, float g_unscale, void* workspace, size_t workspace_bytes, agrl_stream_t stream) {
     AGRL_CHECK_ARG(agrl_lp16_is_f16(), "agrl_distmat_split16: the split planes are fp16 (load libagrl_hip.so, not the bf16 build)");
-    AGRL_CHECK_ARG(D3 > 0 && D3 % 3 == 0 && g_unscale > 0.f && g_unscale <= 3.4e38f, "agrl_distmat_split16: D3 = 3 x columns, g_unscale a positive power of two");
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(frexpf(g_unscale, &e) == 0.5f, "agrl_distmat_split16: g_unscale=%g is not a power of two", (double)g_unscale);
-    }
+    AGRL_CHECK_ARG(D3 > 0 && D3 % 3 == 0, "agrl_distmat_split16: D3 = %d is not 3 x columns", D3);
+    AGRL_CHECK_POW2(g_unscale, "agrl_distmat_split16", "g_unscale");
     return distmat_impl(q3, g3, qn, gn, dist, m, n, D3, ldd, metric, AGRL_LP16, workspace, workspace_bytes, g_unscale, stream);
 }
 

@@ -176,9 +176,6 @@ __device__ inline void load4<lp16_t>(const lp16_t* p, float v[4]) {
     unpack_lp16x2(u.y, v[2], v[3]);
 }
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
 // 16 zero bytes in device memory: the DMA source of every padded / out-of-range chunk
 static __device__ __attribute__((aligned(16))) uint4 g_zero16;
 

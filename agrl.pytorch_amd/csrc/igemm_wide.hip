@@ -550,11 +550,7 @@ int launch_igemm_wide_f32out(const IgemmParams& p, hipStream_t stream, const cha
     // One workgroup per tile and per CU: the launch takes ceil(tiles / CUs) rounds of a tile's time, and a 256 x 192 tile costs 3/4
     // of a 256 x 256 one. The MARS matrix (1980 x 12 180: 8 x 48 = 384 tiles of 256 columns = 1.5 rounds, paid as 2) is 8 x 64 = 512
     // tiles of 192 columns = 2 exact rounds at 3/4 of the cost each: take the 192-column tile whenever it is cheaper by that count.
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    const int cus = agrl_cu_count();
     const int mt = cdiv(p.M, WBM);
     const int tiles256 = mt * cdiv(p.N, 256), tiles192 = mt * cdiv(p.N, 192);
     const long long cost256 = (long long)cdiv(tiles256, cus) * 256, cost192 = (long long)cdiv(tiles192, cus) * 192;
@@ -594,11 +590,7 @@ int launch_igemm_wide(const IgemmParams& p, hipStream_t stream, const char* who)
     if (opt.igemm_wide == 2 && (p.N % WBN) == 0) half_n = false;
     if (opt.igemm_wide == 3 && p.pool_nparts == 0 && !p.x2) half_n = true;
     // persistent form: one workgroup per CU walks its share of the tiles (AGRL_IGEMM_WIDE_PERSIST=0: one per tile)
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    const int n_cu = agrl_cu_count();
     const bool persist = true;  // fewer workgroups than tiles: each walks its XCD's range (one workgroup per tile measured slower)
     const bool res = p.res != nullptr;
     if (half_n) {

@@ -9,8 +9,7 @@
 //   3x3/2 max                               -> NHWC store, 64 channels contiguous per wavefront
 // Out-of-range conv positions are stored as 0, which is exact for a max over post-ReLU values whose
 // window always contains at least one in-range element.
-#include "agrl_common.h"
-#include "frames_u8.h"
+#include "stem_dev.h"
 
 namespace {
 constexpr int PT_H = 4, PT_W = 8;                // pooled tile
@@ -149,19 +148,15 @@ template <typename TIN, typename... EX>
 static int launch_stem(const char* who, const TIN* x, const float* w, const float* bias, void* out, int N, int H, int W, int out_dtype,
                        agrl_stream_t stream, EX... ex) {
     AGRL_CHECK_ARG(x && w && bias && out, "%s: null pointer", who);
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    StemShape s;
+    if (stem_shape(who, N, H, W, PT_H, PT_W, &s)) return 1;
     AGRL_CHECK_ARG(out_dtype == AGRL_F32 || out_dtype == AGRL_LP16, "%s: bad dtype %d", who, out_dtype);
-    const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
-    const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
-    const int tiles_h = cdiv(PH, PT_H), tiles_w = cdiv(PW, PT_W);
-    const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
     if (out_dtype == AGRL_F32)
-        hipLaunchKernelGGL((stem_kernel<float, TIN, EX...>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                           (float*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, ex...);
+        hipLaunchKernelGGL((stem_kernel<float, TIN, EX...>), dim3((unsigned)s.grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
+                           (float*)out, H, W, s.CH, s.CW, s.PH, s.PW, s.tiles_w, s.tiles_h * s.tiles_w, ex...);
     else
-        hipLaunchKernelGGL((stem_kernel<lp16_t, TIN, EX...>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
-                           (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, ex...);
+        hipLaunchKernelGGL((stem_kernel<lp16_t, TIN, EX...>), dim3((unsigned)s.grid), dim3(256), 0, (hipStream_t)stream, x, w, bias,
+                           (lp16_t*)out, H, W, s.CH, s.CW, s.PH, s.PW, s.tiles_w, s.tiles_h * s.tiles_w, ex...);
     AGRL_CHECK_LAUNCH(who);
     return 0;
 }

@@ -12,28 +12,10 @@
 //   -> bf16 conv tile in LDS (overlaying patch+weights) -> 3x3/2 max -> NHWC store (128 B per pooled pixel)
 #include <stdlib.h>
 
-#include "agrl_common.h"
-#include "frames_u8.h"
+#include "stem_dev.h"
 
 namespace {
-constexpr int PT = 8;                 // pooled tile edge
-constexpr int CT = 2 * PT + 1;        // conv tile edge 17
-constexpr int NPOS = CT * CT;         // 289
-constexpr int NFRAG = (NPOS + 15) / 16;  // 19
-constexpr int NWV = 8;                // waves per workgroup
-constexpr int NTH = 64 * NWV;
-constexpr int FPW = (NFRAG + NWV - 1) / NWV;  // position fragments per wave: 3
-constexpr int IT = 2 * (CT - 1) + 7;  // input patch edge 39
-constexpr int PWP = 40;               // padded patch width (pixels)
-constexpr int PATCH_BYTES = IT * PWP * 8;      // 12480
-// 7*32 bf16 = 448 + 32 pad = 30 sixteen-byte slots per row. A ds_read_b128 is served in groups of 16 lanes: rows
-// (lane & 15) 0-3, 12-15 at k-chunk g with rows 4-11 at k-chunk g + 1; 30 r mod 16 sends the first set to the even slots and
-// the second (+1) to the odd ones: conflict-free (29 slots, the "odd stride" choice, collides on five of sixteen)
-constexpr int WROW_BYTES = 480;
-constexpr int W_BYTES = 64 * WROW_BYTES;       // 30720 = 30 KiB
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
+using namespace stem8;  // tile geometry, tile decode, patch prefetch, weight DMA: shared with stem_split16.hip
 
 // Persistent form: a workgroup keeps the packed weights in LDS and walks tiles; the NEXT tile's input pixels are requested
 // (12 floats per thread, in registers) right after the current patch has been written to LDS, so the HBM round trip runs
@@ -47,16 +29,14 @@ constexpr int REGION_BYTES = CT_BYTES > PATCH_BYTES ? CT_BYTES : PATCH_BYTES;
 // two barriers that guarded the overlay (sweep done -> conv tile may be written; pool done -> next patch may be written) disappear: a wave
 // that has finished pooling writes its pixels of the next patch while the others still pool, two barriers per tile instead of four.
 //
-// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument): a thread requests its pixels' BYTES where the fp32 form requests
-// floats, and turns them into the normalised fp32 values one phase later -- a gather from the 3 KB table (L1-resident; in LDS it would
-// cost the SPLIT form its second workgroup per CU) issued behind the conv-tile barrier, when the bytes have had the whole MFMA sweep to
-// land, and in flight under the pooling. Everything from the LDS write of the patch on is the fp32 form's code on the same values.
+// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument; stem8::PatchPrefetch): the gather from the 3 KB table (L1-resident;
+// in LDS it would cost the SPLIT form its second workgroup per CU) is issued behind the conv-tile barrier, when the bytes have had the
+// whole MFMA sweep to land, and is in flight under the pooling. Everything from the LDS write of the patch on is the fp32 form's code.
 template <bool SPLIT, typename TIN, typename... EX>
 __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict__ x, const unsigned char* __restrict__ wpk,
                                                         const float* __restrict__ bias, lp16_t* __restrict__ out, int H,
                                                         int W, int CH, int CW, int PH, int PW, int tiles_w, int tiles_hw,
                                                         int ntiles, int xcd_map, EX... ex) {
-    constexpr bool U8 = sizeof...(EX) != 0;
     constexpr int TILES_BYTES = SPLIT ? PATCH_BYTES + CT_BYTES : REGION_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char smem[TILES_BYTES + W_BYTES + 256];
     unsigned char* s_patch = smem;
@@ -70,67 +50,13 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = gridDim.x;
 
-    // weights: 30 one-KiB DMA pieces, contiguous, once per workgroup
-    for (int piece = wave; piece < W_BYTES / 1024; piece += NWV)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(wpk + piece * 1024 + lane * 16), (lds_void_t*)(s_w + piece * 1024), 16, 0, 0);
-
+    weights_to_lds(wpk, s_w, wave, lane);  // once per workgroup
     if (tid < 64) s_bias[tid] = bias[tid];
-    // patch: one pixel (3 channels -> 4 bf16) per thread per pass; all loads of all passes are issued together
-    constexpr int NPASS = (IT * PWP + NTH - 1) / NTH;  // 4
-    float pv[NPASS][3];
-    uint32_t pb[U8 ? NPASS : 1][3];  // uint8 frames: the raw bytes, FRAMES_U8_PAD (the table's zero entry) outside the frame
-    auto load_patch = [&](int T) {
-        const int n = T / tiles_hw;
-        const int trem = T - n * tiles_hw;
-        const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
-        const int iy0 = 2 * (2 * ph0 - 1) - 3, ix0 = 2 * (2 * pw0 - 1) - 3;
-        const TIN* xn = x + (size_t)n * 3 * H * W;
-        int td = tid;
-        asm volatile("" : "+v"(td));  // per-tile address arithmetic (hoisted out of the tile loop it costs 100 registers)
-#pragma unroll
-        for (int i = 0; i < NPASS; ++i) {
-            const int e = td + NTH * i;
-            const int py = e / PWP, px = e - py * PWP;
-            const int iy = iy0 + py, ix = ix0 + px;
-            if constexpr (U8) {
-                const FramesU8 u8 = frames_u8_of(ex...);
-                pb[i][0] = pb[i][1] = pb[i][2] = FRAMES_U8_PAD;
-                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                    const uint32_t o = (uint32_t)(iy * W + ix) * u8.pixel_stride;   // inside one frame: < 3 H W < 2^31 (frames_u8_args)
-                    pb[i][0] = xn[o];
-                    pb[i][1] = xn[o + (uint32_t)u8.channel_stride];
-                    pb[i][2] = xn[o + 2 * (uint32_t)u8.channel_stride];
-                }
-            } else {
-                pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
-                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                    const size_t o = (size_t)iy * W + ix;
-                    pv[i][0] = xn[o];
-                    pv[i][1] = xn[(size_t)H * W + o];
-                    pv[i][2] = xn[2 * (size_t)H * W + o];
-                }
-            }
-        }
-    };
-    auto normalize_patch = [&]() {  // uint8 frames: bytes -> table values (the fp32 form's pv)
-        if constexpr (U8) {
-            const FramesU8 u8 = frames_u8_of(ex...);
-#pragma unroll
-            for (int i = 0; i < NPASS; ++i)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) pv[i][c] = u8.table[c * FRAMES_U8_ROW + pb[i][c]];
-        }
-    };
+    PatchPrefetch<TIN, EX...> pre;  // one pixel (3 channels -> 4 bf16) per thread per pass
+    constexpr bool U8 = decltype(pre)::U8;
     const int frow = lane & 15, g = lane >> 4;
     int a_off[FPW];  // byte offset of this lane's patch slice at filter row 0
-#pragma unroll
-    for (int i = 0; i < FPW; ++i) {
-        int pos = (wave + NWV * i) * 16 + frow;
-        pos = pos < NPOS ? pos : NPOS - 1;
-        const int cy = pos / CT, cx = pos - cy * CT;
-        a_off[i] = ((2 * cy) * PWP + 2 * cx + 2 * g) * 8;
-    }
-    auto ct_row = [](int pos) { return (pos & ~3) | ((pos & 1) << 1) | ((pos >> 1) & 1); };
+    patch_frag_offsets(wave, frow, g, a_off);
 
     // Tile order. Neighbouring tiles share 7 of their 39 input columns / rows, and a 39-pixel row segment of a tile straddles 2-3 of the
     // 4 128-byte lines of its image row: with tile T on workgroup T mod G (XCD T mod 8) the four tiles across an image row sat on four
@@ -149,15 +75,12 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict
     };
     int q = xmap ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (q < qlimit) {
-        load_patch(tile_of(q));
-        normalize_patch();
+        pre.load(x, H, W, tile_at(tile_of(q), tiles_w, tiles_hw), ex...);
+        pre.normalize(ex...);
     }
     for (; q < qlimit; q += qstep) {
-        const int T = tile_of(q);
-        const int n = T / tiles_hw;
-        const int trem = T - n * tiles_hw;
-        const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
-        const int cr0 = 2 * ph0 - 1, cc0 = 2 * pw0 - 1;
+        const Tile t = tile_at(tile_of(q), tiles_w, tiles_hw);
+        const int n = t.n, ph0 = t.ph0, pw0 = t.pw0, cr0 = t.cr0, cc0 = t.cc0;
         // ---- this tile's pixels (requested one tile ago) -> bf16 patch in LDS
         int tw = tid;
         if constexpr (U8) asm volatile("" : "+v"(tw));  // the uint8 form has no register to spare for hoisted LDS addresses
@@ -166,14 +89,15 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict
             const int e = tw + NTH * i;
             if (e < IT * PWP) {
                 uint2 u;
-                u.x = pack_lp16x2(pv[i][0], pv[i][1]);
-                u.y = (uint32_t)f32_to_lp16(pv[i][2]);
+                u.x = pack_lp16x2(pre.pv[i][0], pre.pv[i][1]);
+                u.y = (uint32_t)f32_to_lp16(pre.pv[i][2]);
                 *reinterpret_cast<uint2*>(s_patch + e * 8) = u;
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first tile: the weight DMA (invisible to the compiler) has landed
         __syncthreads();
-        if (q + qstep < qlimit) load_patch(tile_of(q + qstep));  // in flight until the top of the next iteration
+        // the next tile's pixels: in flight until the top of the next iteration
+        if (q + qstep < qlimit) pre.load(x, H, W, tile_at(tile_of(q + qstep), tiles_w, tiles_hw), ex...);
 
         f32x4_t acc[FPW][4];
 #pragma unroll
@@ -232,7 +156,7 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict
             }
         }
         __syncthreads();
-        if (q + qstep < qlimit) normalize_patch();  // uint8 frames: the next tile's bytes have landed under the sweep
+        if (q + qstep < qlimit) pre.normalize(ex...);  // uint8 frames: the next tile's bytes have landed under the sweep
 
         // 3x3/2 max pool: thread -> 8 channels (one 16-byte slot) of ONE pooled pixel. The activations are post-ReLU bf16,
         // i.e. non-negative: their bit patterns order like unsigned 16-bit integers, so the maximum is two v_pk_max_u16 per
@@ -269,24 +193,20 @@ template <typename TIN, typename... EX>
 static int launch_stem_mfma(const char* who, const TIN* x, const void* w_packed, const float* bias, void* out, int N, int H, int W,
                             agrl_stream_t stream, EX... ex) {
     AGRL_CHECK_ARG(x && w_packed && bias && out, "%s: null pointer", who);
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    StemShape s;
+    if (stem_shape(who, N, H, W, PT, PT, &s)) return 1;
     AGRL_CHECK_ARG((((uintptr_t)w_packed) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
                    "%s: misaligned pointer", who);
-    const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
-    const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
-    const int tiles_h = cdiv(PH, PT), tiles_w = cdiv(PW, PT);
-    const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
     const int wgs = 512;  // two persistent workgroups per CU (67 KB of LDS each)
-    const unsigned launch = (unsigned)(grid < wgs ? grid : wgs);
+    const unsigned launch = (unsigned)(s.grid < wgs ? s.grid : wgs);
     if (agrl_opts().stem_split_lds != 0)
         hipLaunchKernelGGL((stem_mfma_kernel<true, TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
-                       (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w,
-                       (int)grid, agrl_opts().stem_xcd_map != 0, ex...);
+                       (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, s.CH, s.CW, s.PH, s.PW, s.tiles_w, s.tiles_h * s.tiles_w,
+                       s.grid, agrl_opts().stem_xcd_map != 0, ex...);
     else
         hipLaunchKernelGGL((stem_mfma_kernel<false, TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x,
-                       (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w,
-                       (int)grid, agrl_opts().stem_xcd_map != 0, ex...);
+                       (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, s.CH, s.CW, s.PH, s.PW, s.tiles_w, s.tiles_h * s.tiles_w,
+                       s.grid, agrl_opts().stem_xcd_map != 0, ex...);
     AGRL_CHECK_LAUNCH(who);
     return 0;
 }

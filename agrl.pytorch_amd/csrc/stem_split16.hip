@@ -11,26 +11,12 @@
 // LDS 25 + 60 + 37 KB: one 512-thread workgroup per CU, persistent over tiles, the next tile's pixels prefetched into registers.
 #include <stdlib.h>
 
-#include "agrl_common.h"
-#include "frames_u8.h"
+#include "stem_dev.h"
 
 namespace {
-constexpr int PT = 8;                 // pooled tile edge
-constexpr int CT = 2 * PT + 1;        // conv tile edge 17
-constexpr int NPOS = CT * CT;         // 289
-constexpr int NFRAG = (NPOS + 15) / 16;  // 19
-constexpr int NWV = 8;
-constexpr int NTH = 64 * NWV;
-constexpr int FPW = (NFRAG + NWV - 1) / NWV;  // 3
-constexpr int IT = 2 * (CT - 1) + 7;  // 39
-constexpr int PWP = 40;
-constexpr int PATCH_BYTES = IT * PWP * 8;      // 12480
-constexpr int WROW_BYTES = 480;                // stem_mfma.hip: the conflict-free row stride of the packed weights
-constexpr int W_BYTES = 64 * WROW_BYTES;       // 30 KiB
-constexpr int CT_BYTES = (NPOS + 3) * 128;     // [pos][32 channels] fp32
+using namespace stem8;  // tile geometry, tile decode, patch prefetch, weight DMA: shared with stem_mfma.hip
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
+constexpr int CT_BYTES = (NPOS + 3) * 128;     // [pos][32 channels] fp32
 
 __device__ __forceinline__ f32x4_t mfma_f16_16x16x32(const uint4& a, const uint4& b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
@@ -41,9 +27,8 @@ __device__ __forceinline__ uint32_t pack_f16x2(float a, float b) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
-// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument): as in stem_mfma.hip -- the next tile's BYTES are requested where
-// the fp32 form requests floats, and become the normalised fp32 values through a gather from the 3 KB table issued behind the first
-// channel half's conv-tile barrier (the bytes have had that half's MFMA sweep to land). The rest is the fp32 form's code.
+// TIN = unsigned char (uint8 frames, one trailing FramesU8 argument; stem8::PatchPrefetch): the gather from the 3 KB table is issued
+// behind the first channel half's conv-tile barrier (the bytes have had that half's MFMA sweep to land). The rest is the fp32 form's code.
 template <typename TIN, typename... EX>
 __global__ __launch_bounds__(NTH) void stem_split16_kernel(const TIN* __restrict__ x, const unsigned char* __restrict__ wh_pk,
                                                            const unsigned char* __restrict__ wl_pk, const float* __restrict__ bias,
@@ -63,99 +48,43 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const TIN* __restrict
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = gridDim.x;
 
-    for (int piece = wave; piece < W_BYTES / 1024; piece += NWV) {
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(wh_pk + piece * 1024 + lane * 16), (lds_void_t*)(s_wh + piece * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(wl_pk + piece * 1024 + lane * 16), (lds_void_t*)(s_wl + piece * 1024), 16, 0, 0);
-    }
+    weights_to_lds(wh_pk, s_wh, wave, lane);
+    weights_to_lds(wl_pk, s_wl, wave, lane);
     if (tid < 64) s_bias[tid] = bias[tid];
 
-    constexpr int NPASS = (IT * PWP + NTH - 1) / NTH;  // 4
-    float pv[NPASS][3];
-    uint32_t pb[U8 ? NPASS : 1][3];  // uint8 frames: the raw bytes, FRAMES_U8_PAD (the table's zero entry) outside the frame
-    auto load_patch = [&](int T) {
-        const int n = T / tiles_hw;
-        const int trem = T - n * tiles_hw;
-        const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
-        const int iy0 = 2 * (2 * ph0 - 1) - 3, ix0 = 2 * (2 * pw0 - 1) - 3;
-        const TIN* xn = x + (size_t)n * 3 * H * W;
-        int td = tid;
-        asm volatile("" : "+v"(td));
-#pragma unroll
-        for (int i = 0; i < NPASS; ++i) {
-            const int e = td + NTH * i;
-            const int py = e / PWP, px = e - py * PWP;
-            const int iy = iy0 + py, ix = ix0 + px;
-            if constexpr (U8) {
-                const FramesU8 u8 = frames_u8_of(ex...);
-                pb[i][0] = pb[i][1] = pb[i][2] = FRAMES_U8_PAD;
-                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                    const uint32_t o = (uint32_t)(iy * W + ix) * u8.pixel_stride;   // inside one frame: < 3 H W < 2^31 (frames_u8_args)
-                    pb[i][0] = xn[o];
-                    pb[i][1] = xn[o + (uint32_t)u8.channel_stride];
-                    pb[i][2] = xn[o + 2 * (uint32_t)u8.channel_stride];
-                }
-            } else {
-                pv[i][0] = pv[i][1] = pv[i][2] = 0.f;
-                if (e < IT * PWP && px < IT && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                    const size_t o = (size_t)iy * W + ix;
-                    pv[i][0] = xn[o];
-                    pv[i][1] = xn[(size_t)H * W + o];
-                    pv[i][2] = xn[2 * (size_t)H * W + o];
-                }
-            }
-        }
-    };
-    auto normalize_patch = [&]() {  // uint8 frames: bytes -> table values (the fp32 form's pv)
-        if constexpr (U8) {
-            const FramesU8 u8 = frames_u8_of(ex...);
-#pragma unroll
-            for (int i = 0; i < NPASS; ++i)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) pv[i][c] = u8.table[c * FRAMES_U8_ROW + pb[i][c]];
-        }
-    };
+    PatchPrefetch<TIN, EX...> pre;
     const int frow = lane & 15, g = lane >> 4;
     int a_off[FPW];
-#pragma unroll
-    for (int i = 0; i < FPW; ++i) {
-        int pos = (wave + NWV * i) * 16 + frow;
-        pos = pos < NPOS ? pos : NPOS - 1;
-        const int cy = pos / CT, cx = pos - cy * CT;
-        a_off[i] = ((2 * cy) * PWP + 2 * cx + 2 * g) * 8;
-    }
-    auto ct_row = [](int pos) { return (pos & ~3) | ((pos & 1) << 1) | ((pos >> 1) & 1); };
+    patch_frag_offsets(wave, frow, g, a_off);
 
     int q = blockIdx.x;
     if (q < ntiles) {
-        load_patch(q);
-        normalize_patch();
+        pre.load(x, H, W, tile_at(q, tiles_w, tiles_hw), ex...);
+        pre.normalize(ex...);
     }
     for (; q < ntiles; q += G) {
-        const int T = q;
-        const int n = T / tiles_hw;
-        const int trem = T - n * tiles_hw;
-        const int ph0 = (trem / tiles_w) * PT, pw0 = (trem % tiles_w) * PT;
-        const int cr0 = 2 * ph0 - 1, cc0 = 2 * pw0 - 1;
+        const Tile t = tile_at(q, tiles_w, tiles_hw);
+        const int n = t.n, ph0 = t.ph0, pw0 = t.pw0, cr0 = t.cr0, cc0 = t.cc0;
         // ---- this tile's pixels (requested one tile ago) -> fp16 hi / lo patches in LDS
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
             const int e = tid + NTH * i;
             if (e < IT * PWP) {
                 typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-                const h2_t h01 = {(_Float16)pv[i][0], (_Float16)pv[i][1]};
-                const _Float16 h2 = (_Float16)pv[i][2];
+                const h2_t h01 = {(_Float16)pre.pv[i][0], (_Float16)pre.pv[i][1]};
+                const _Float16 h2 = (_Float16)pre.pv[i][2];
                 uint2 uh, ul;
                 uh.x = __builtin_bit_cast(uint32_t, h01);
                 uh.y = (uint32_t)__builtin_bit_cast(unsigned short, h2);
-                ul.x = pack_f16x2(pv[i][0] - (float)h01[0], pv[i][1] - (float)h01[1]);
-                ul.y = (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)(pv[i][2] - (float)h2));
+                ul.x = pack_f16x2(pre.pv[i][0] - (float)h01[0], pre.pv[i][1] - (float)h01[1]);
+                ul.y = (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)(pre.pv[i][2] - (float)h2));
                 *reinterpret_cast<uint2*>(s_ph + e * 8) = uh;
                 *reinterpret_cast<uint2*>(s_pl + e * 8) = ul;
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first tile: the weight DMA (invisible to the compiler) has landed
         __syncthreads();
-        if (q + G < ntiles) load_patch(q + G);  // in flight until the top of the next iteration
+        if (q + G < ntiles) pre.load(x, H, W, tile_at(q + G, tiles_w, tiles_hw), ex...);  // in flight until the top of the next iteration
 
         const bool interior = cr0 >= 0 && cc0 >= 0 && cr0 + CT <= CH && cc0 + CT <= CW;
 #pragma unroll 1
@@ -212,7 +141,7 @@ __global__ __launch_bounds__(NTH) void stem_split16_kernel(const TIN* __restrict
             }
             __syncthreads();
             if constexpr (U8) {
-                if (half == 0 && q + G < ntiles) normalize_patch();  // the next tile's bytes have landed under the sweep
+                if (half == 0 && q + G < ntiles) pre.normalize(ex...);  // the next tile's bytes have landed under the sweep
             }
             // 3x3/2 max pool: thread -> 4 channels (one 16-byte slot) of one pooled pixel
             {
@@ -245,26 +174,14 @@ template <typename TIN, typename... EX>
 static int launch_stem_split16(const char* who, const TIN* x, const void* wh_packed, const void* wl_packed, const float* bias, float* out,
                                int N, int H, int W, float w_unscale, agrl_stream_t stream, EX... ex) {
     AGRL_CHECK_ARG(x && wh_packed && wl_packed && bias && out, "%s: null pointer", who);
-    AGRL_CHECK_ARG(N > 0 && H >= 7 && W >= 7, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    StemShape s;
+    if (stem_shape(who, N, H, W, PT, PT, &s)) return 1;
     AGRL_CHECK_ARG(((((uintptr_t)wh_packed) | ((uintptr_t)wl_packed) | ((uintptr_t)bias) | ((uintptr_t)out)) & 15) == 0, "%s: misaligned pointer", who);
-    AGRL_CHECK_ARG(w_unscale > 0.f && w_unscale <= 3.4e38f, "%s: w_unscale must be a positive finite power of two", who);
-    {
-        int e = 0;
-        AGRL_CHECK_ARG(frexpf(w_unscale, &e) == 0.5f, "%s: w_unscale=%g is not a power of two", who, (double)w_unscale);
-    }
-    const int CH = (H + 6 - 7) / 2 + 1, CW = (W + 6 - 7) / 2 + 1;
-    const int PH = (CH + 2 - 3) / 2 + 1, PW = (CW + 2 - 3) / 2 + 1;
-    const int tiles_h = cdiv(PH, PT), tiles_w = cdiv(PW, PT);
-    const long long grid = (long long)N * tiles_h * tiles_w;
-    AGRL_CHECK_ARG(grid < (1ll << 31), "%s: grid too large", who);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    const unsigned launch = (unsigned)(grid < cus ? grid : cus);   // one persistent workgroup per CU (123 KB of LDS)
+    AGRL_CHECK_POW2(w_unscale, who, "w_unscale");
+    const int cus = agrl_cu_count();
+    const unsigned launch = (unsigned)(s.grid < cus ? s.grid : cus);   // one persistent workgroup per CU (123 KB of LDS)
     hipLaunchKernelGGL((stem_split16_kernel<TIN, EX...>), dim3(launch), dim3(NTH), 0, (hipStream_t)stream, x, (const unsigned char*)wh_packed,
-                       (const unsigned char*)wl_packed, bias, out, w_unscale, H, W, CH, CW, PH, PW, tiles_w, tiles_h * tiles_w, (int)grid, ex...);
+                       (const unsigned char*)wl_packed, bias, out, w_unscale, H, W, s.CH, s.CW, s.PH, s.PW, s.tiles_w, s.tiles_h * s.tiles_w, s.grid, ex...);
     AGRL_CHECK_LAUNCH(who);
     return 0;
 }

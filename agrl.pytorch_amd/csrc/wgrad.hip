@@ -196,11 +196,10 @@ template <typename TIN, int BM, int BN>
 static int wgrad_capacity_of() {
     static int cap = 0;
     if (cap == 0) {
-        int dev = 0, cus = 256, per_cu = 2;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        int per_cu = 2;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wgrad_tn_kernel<TIN, BM, BN>, 512, 0) != hipSuccess || per_cu < 1) per_cu = 2;
         (void)hipGetLastError();
-        cap = per_cu * (cus > 0 ? cus : 256);
+        cap = per_cu * agrl_cu_count();
     }
     return cap;
 }

@@ -166,12 +166,17 @@ def _stem_frames(x, mean, std):
     return x, x.shape[0], x.shape[2], x.shape[3], 4.0, None
 
 
+def stem_out_shape(H, W):
+    """(H, W) of a frame -> (CH, CW, PH, PW): the 7x7/2 pad-3 conv map and the 3x3/2 pad-1 max-pooled map of the three stems."""
+    CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    return CH, CW, (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
+
+
 def stem(x_nchw, w_ohwi, bias, out_dtype, mean=PIXEL_MEAN, std=PIXEL_STD):
     """(N,3,H,W) fp32 NCHW -- or uint8 frames, (N,3,H,W) / (N,H,W,3), normalised with ``frame_table(mean, std)`` while the kernel stages
     them -> (N,PH,PW,64) NHWC. vmgn.py:281-284."""
     x_nchw, N, H, W, _, u8 = _stem_frames(x_nchw, mean, std)
-    CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
+    _, _, PH, PW = stem_out_shape(H, W)
     out = torch.empty((N, PH, PW, 64), dtype=out_dtype, device=x_nchw.device)
     with _dev(x_nchw):
         if u8 is not None:
@@ -219,8 +224,7 @@ def stem_lp16(x_nchw, w_packed, bias, mean=PIXEL_MEAN, std=PIXEL_STD):
     16-bit type (LP_DTYPE). vmgn.py:281-284."""
     assert w_packed.dtype == LP_DTYPE and tuple(w_packed.shape) == (64, 240)
     x_nchw, N, H, W, ebytes, u8 = _stem_frames(x_nchw, mean, std)
-    CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
+    CH, CW, PH, PW = stem_out_shape(H, W)
     out = torch.empty((N, PH, PW, 64), dtype=LP_DTYPE, device=x_nchw.device)
     if _hip.PROFILE is not None:
         _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": ebytes * x_nchw.numel() + 2.0 * out.numel() + 2.0 * w_packed.numel(),
@@ -355,8 +359,7 @@ def stem_split16(x_nchw, wh_packed, wl_packed, unscale, bias, mean=PIXEL_MEAN, s
     """Split-fp16 stem: (N,3,H,W) fp32 NCHW -- or uint8 frames in either layout, as in ``stem`` -> (N,PH,PW,64) fp32 NHWC
     (agrl_stem_split16). vmgn.py:281-284."""
     x_nchw, N, H, W, ebytes, u8 = _stem_frames(x_nchw, mean, std)
-    CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
+    CH, CW, PH, PW = stem_out_shape(H, W)
     out = torch.empty((N, PH, PW, 64), dtype=torch.float32, device=x_nchw.device)
     if _hip.PROFILE is not None:
         _hip.PROFILE_TAG = {"flops": 2.0 * N * CH * CW * 64 * 147, "bytes": ebytes * x_nchw.numel() + 4.0 * out.numel() + 4.0 * wh_packed.numel(),

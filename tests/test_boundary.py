@@ -337,6 +337,19 @@ def test_host_side_helpers_without_gpu():
     assert torch.equal(pool_clips(f, 3, "max"), torch.stack([f[0:3].max(0)[0], f[3:6].max(0)[0]]))
 
 
+@pytest.mark.parametrize("hw", [(7, 7), (8, 9), (37, 29), (64, 48), (130, 70), (256, 128)])
+def test_stem_out_shape_matches_conv_and_maxpool(hw):
+    """hip_ops.stem_out_shape, the one place the three stem wrappers size their outputs from, against the shapes torch itself gives
+    conv 7x7/2 pad 3 and maxpool 3x3/2 pad 1 (vmgn.py:281-284)."""
+    import torch.nn.functional as F
+    from torchreid import hip_ops as ops
+    H, W = hw
+    conv = F.conv2d(torch.zeros(1, 3, H, W), torch.zeros(64, 3, 7, 7), stride=2, padding=3)
+    pooled = F.max_pool2d(conv, 3, 2, 1)
+    CH, CW, PH, PW = ops.stem_out_shape(H, W)
+    assert (CH, CW) == tuple(conv.shape[2:]) and (PH, PW) == tuple(pooled.shape[2:])
+
+
 def test_attn_tail_switch_is_cached_until_reload(monkeypatch):
     """Round-5 review (dispatch sprawl): the Python-side AGRL_HIP_* switches (AGRL_HIP_FUSE_ATTN_TAIL here) are read from the environment
     once, like the library's own, instead of once per forward; _hip.reload_options() drops the cache together with the library's."""

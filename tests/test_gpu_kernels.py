@@ -1547,11 +1547,12 @@ def test_fp16_mfma_keeps_subnormal_operands():
     assert torch.all(out.float() == 0.0625)
 
 
-@pytest.mark.parametrize("shape", [(3, 256, 128), (2, 64, 32), (1, 37, 23), (2, 130, 70)])
+@pytest.mark.parametrize("shape", [(3, 256, 128), (2, 64, 32), (1, 37, 23), (2, 130, 70), (70, 64, 48), (300, 37, 29)])
 def test_stem_split16_matches_float64(shape):
     """agrl_stem_split16 (round 6: the stem as three fp16 MFMAs per product, fp32 out; vmgn.py:281-284) against conv 7x7/2 + ReLU +
     maxpool 3x3/2 in FLOAT64 and beside the exact-fp32 stem (agrl_stem_conv_bn_relu_maxpool): image borders, ragged tiles, a weight row
-    a thousand times smaller than the rest."""
+    a thousand times smaller than the rest. The last two shapes make 280 and 600 tiles -- more than the one workgroup per CU the kernel
+    launches -- so the persistent loop (the next tile's prefetch under this tile's sweep, the closing barrier) is held to float64 too."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(H * W)
