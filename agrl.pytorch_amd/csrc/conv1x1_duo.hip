@@ -39,7 +39,7 @@
 //     ride out the queueing behind HBM-latency requests, and the LDS cannot hold a tile's worth of operands ahead. What is left
 //     is fewer bytes per CU (the 256 x 256 tile of igemm_wide_kernel moves 3 MB per CU, this 128 x 256 tile 4 MB) or fewer HBM
 //     bytes per launch (the pooled form: no result map) -- which is where this kernel wins.
-#include "fat_dev.h"
+#include "fat1x1_dev.h"
 
 namespace {
 
@@ -74,37 +74,9 @@ struct DuoParams {
 #ifndef DUO_ABL
 #define DUO_ABL 0  // timing ablations (results wrong; tools/duo_ablate.sh): 1 no residual loads, 2 no stores, 4 no MFMA, 8 no weight loads in the loop, 16 no pixel DMA in the loop, 32 one workgroup per CU (48 KB of dynamic LDS on top), 64 phase stamps (agrl_duo_trace_buffer, tools/duo_timeline.py)
 #endif
-constexpr int DRING = 8;                 // weight fragments in flight per wave
-constexpr int DPS = 4 * 4;               // weight fragments per 128-channel slab and wave: 4 k-steps x 4 channel fragments
-constexpr int DROWS = 128;               // pixel rows per tile
-constexpr int DHALF = DROWS * 128;       // 128 pixel rows x 64 channels
-constexpr int DSLAB = 2 * DHALF;         // one 128-channel slab of the pixel tile: 32 KB
-constexpr int DPPW = 8;                  // DMA pieces (8 rows x 128 B) per wave and slab
-constexpr int DBARRIER_AT = 12;          // see conv1x1_fat.hip
-constexpr int dpieces_at(int p) { return p >= DBARRIER_AT ? 2 : 0; }
-constexpr int dpiece_first(int p) { int n = 0; for (int q = 0; q < p; ++q) n += dpieces_at(q); return n; }
-static_assert(dpiece_first(DPS) == DPPW && DBARRIER_AT >= DRING, "all pieces placed, behind fragments whose successors' ring slots the prologue fills");
-struct DuoSched {
-    int allowed[DPS];
-};
-constexpr DuoSched make_duo_sched() {  // vmcnt budget of the wait in front of fragment p of a slab (steady state)
-    DuoSched s{};
-    int issued[4][DPS] = {};
-    int seq = 0;
-    for (int p = 0; p < DRING; ++p) issued[0][p] = seq++;
-    for (int k = 0; k < 3; ++k)
-        for (int p = 0; p < DPS; ++p) {
-            if (k == 1) s.allowed[p] = seq - 1 - issued[k][p];
-            const int q = p + DRING;
-            if (q >= DPS) issued[k + 1][q - DPS] = seq++;
-            else issued[k][q] = seq++;
-            seq += dpieces_at(p);  // the next slab's pieces
-        }
-    return s;
-}
-struct DuoSchedOf {
-    static constexpr DuoSched value = make_duo_sched();
-};
+using Duo = Fat1x1<8>;   // the tile, the wait table and the slab body (fat1x1_dev.h): 128 pixel rows, 2 x 32 KB of LDS, 8 DMA pieces per wave and slab
+static_assert(Duo::piece_first(F1PS) == Duo::PPW && F1BARRIER_AT >= F1RING, "all pieces placed, behind fragments whose successors' ring slots the prologue fills");
+constexpr int DUO_F1ABL = ((DUO_ABL & 4) ? F1_NO_MFMA : 0) | ((DUO_ABL & 8) ? F1_NO_WLOAD : 0) | ((DUO_ABL & 16) ? F1_NO_DMA : 0);
 
 #if DUO_ABL & 64   // profiling build: per-workgroup phase stamps (s_memtime) + placement, 12 x 8 bytes per workgroup
 __device__ unsigned long long* g_duo_trace = nullptr;
@@ -116,11 +88,41 @@ __device__ unsigned long long* g_duo_trace = nullptr;
 #define DUO_STAMP(k) do { } while (0)
 #endif
 
+// one cell of the 16-bit epilogue: quads (QLO, QHI) + bias (+ the residual waiting in `cell`) (ReLU), rounded once into `cell`; POOL: the
+// ROUNDED activations (what a separate pooling pass would read) are summed into ps
+template <int QLO, int QHI, bool POOL>
+__device__ __forceinline__ void duo_combine(lds_u32x4_t* cell, float alpha, const float4& b0, const float4& b1, bool has_res, int relu, bool has_out,
+                                            float (&ps)[8]) {
+    float v[8];
+    fat_bias8<QLO, QHI>(v, alpha, b0, b1);   // (alpha = 1: acc + b bit for bit)
+    if (has_res) {
+        const u32x4_t r = *cell;
+        fat_add_lp16x8(v, r);
+    }
+    fat_relu8(v, relu);
+    const uint4 p4 = fat_pack8(v);
+    const u32x4_t pk = {p4.x, p4.y, p4.z, p4.w};
+    if (has_out) *cell = pk;
+    if constexpr (POOL) fat_add_lp16x8(ps, pk);
+}
+// POOL: sum over the 16 pixel lanes of a fragment (same f); lanes frow == 0 park the eight channel sums at d (igemm_wide_kernel<16384>'s order)
+__device__ __forceinline__ void duo_quarter_park(float (&ps)[8], int frow, float* d) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float t = ps[e];
+        t += __shfl_xor(t, 1, 64); t += __shfl_xor(t, 2, 64); t += __shfl_xor(t, 4, 64); t += __shfl_xor(t, 8, 64);
+        ps[e] = t;
+    }
+    if (frow == 0) {
+        *reinterpret_cast<float4*>(d) = make_float4(ps[0], ps[1], ps[2], ps[3]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(ps[4], ps[5], ps[6], ps[7]);
+    }
+}
+
 template <bool POOL, bool PLANES = false>   // PLANES: the split-fp16 epilogue (its own instantiations: both epilogues in one kernel do not fit the 128 arch VGPRs beside the 128 asm-owned AGPRs)
 __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) {
-    using SCHED = DuoSchedOf;
     using std::integral_constant;
-    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * DSLAB];
+    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * Duo::SLAB];
     // pooled planes form: the quarter sums of a pass are parked here (4 waves x [4 quarters][64 channels]) -- the wave's image is the
     // residual planes' landing zone in both passes, and carrying all 64 sums per lane through them overflows the 128 arch VGPRs
     __shared__ __attribute__((aligned(16))) float s_pool_[(POOL && PLANES) ? 4 * 256 : 4];
@@ -146,24 +148,18 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
     // tile = (pixel tile mt, channel tile nt): neighbouring workgroups (same XCD: blockIdx % 8) share the pixel tile
     DUO_STAMP(1);
     const int nNt = p.Cout >> 8;
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, within = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-    }
+    const int bid = fat_xcd_tile(blockIdx.x, gridDim.x);
     const int mt = bid / nNt, nt = bid - mt * nNt;
-    const int m0 = mt * DROWS;
+    const int m0 = mt * Duo::ROWS;
 
-    // ---- pixel staging: piece i = 2 j + h of this wave -> rows (wave + 4 j) * 8 .. + 7 of 64-channel half h; lane (lrow = lane >> 3,
-    // lchk = lane & 7) fetches chunk lchk ^ swizzle(row) of its row (16-byte chunk c of row r at c ^ ((r >> 1) & 7))
+    // ---- pixel staging (Duo::stage): byte offset of the lane's row in x / x2 (+ its swizzled chunk)
     unsigned roff[4], roff2[4];
     const int lrow = lane >> 3, lchk = lane & 7;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int row = (wave + 4 * j) * 8 + lrow;
         const int gm = min(m0 + row, p.M - 1);
-        const unsigned sw = (unsigned)((lchk ^ ((row >> 1) & 7)) << 4);
+        const unsigned sw = Duo::swz(row, lchk);
         unsigned srow = (unsigned)gm;
         if (p.gHoWo) {
             const unsigned f = (unsigned)gm / (unsigned)p.gHoWo, r = (unsigned)gm - f * (unsigned)p.gHoWo;
@@ -187,92 +183,55 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
             }
         }
         const unsigned char* src = second ? p.x2 + roff2[J] + (size_t)((slab - nslab1) * 256 + H * 128) : p.x + roff[J] + (size_t)(slab1 * 256 + H * 128);
-        fat_dma(src, __builtin_amdgcn_readfirstlane(lds0 + buf * DSLAB + H * DHALF + (wave + 4 * J) * 1024));
+        Duo::stage<I>(src, lds0, buf, wave);
     };
+    const int xbase = Duo::xbase(frow, fchunk);
 
-    // ---- pixel fragment b (rows 16 b + (lane & 15)) of k-step kk: half kk >> 1, chunk 4 (kk & 1) + (lane >> 4)
-    const int xbase = frow * 128 + ((fchunk ^ ((frow >> 1) & 7)) << 4);
-
-    // ---- weight stream of this wave: fragment q of slab s at wpk + ((nt * 4 + wave) * nslab * DPS + s * DPS + q) KiB
-    const unsigned char* wstream = p.wpk + (size_t)(nt * 4 + wave) * nslab * (DPS * 1024);
+    // ---- weight stream of this wave: fragment q of slab s at wpk + ((nt * 4 + wave) * nslab * F1PS + s * F1PS + q) KiB
+    const unsigned char* wstream = p.wpk + (size_t)(nt * 4 + wave) * nslab * (F1PS * 1024);
 #if DUO_ABL   // (profiling builds: with parts of the loop compiled out hipcc no longer proves the stream pointer uniform)
     wstream = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)((size_t)wstream >> 32)) << 32) |
                                                      (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(size_t)wstream));   // (the builtin returns a SIGNED int)
 #endif
-    u32x4_t wr[DRING];
-    auto issue_w = [&](auto slot_c, const unsigned char* slab_base, auto pos_c) {
-        constexpr int SLOT = decltype(slot_c)::value, POS = decltype(pos_c)::value;
-        fat_gload<(POS & 3) * 1024>(wr[SLOT], lane16, slab_base + (POS & ~3) * 1024);
-    };
+    u32x4_t wr[F1RING];
 
     asm volatile("" ::: "a127");
     sfor<32>([&](auto qc) { fat_zero<decltype(qc)::value>(); });
 
     // ---- prologue: slab 0's pixel rows; then the first ring of weight fragments with slab 1's pieces behind fragments 4 .. 7 --
     // the order the loop issues them in behind fragments 12 .. 15 of the slab before, so that its counted waits hold from slab 0 on
-    sfor<DPPW>([&](auto ic) { stage_piece(0, 0, ic); });
-    sfor<DRING>([&](auto ic) {
+    sfor<Duo::PPW>([&](auto ic) { stage_piece(0, 0, ic); });
+    sfor<F1RING>([&](auto ic) {
         constexpr int I = decltype(ic)::value;
-        issue_w(ic, wstream, ic);
-        sfor<dpieces_at(I + DRING)>([&](auto jc) {
-            stage_piece(nslab > 1 ? 1 : 0, 1, integral_constant<int, dpiece_first(I + DRING) + decltype(jc)::value>{});
+        Duo::issue_w<I>(wr[I], lane16, wstream);
+        sfor<Duo::pieces_at(I + F1RING)>([&](auto jc) {
+            stage_piece(nslab > 1 ? 1 : 0, 1, integral_constant<int, Duo::piece_first(I + F1RING) + decltype(jc)::value>{});
         });
     });
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DRING + DPPW) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1RING + Duo::PPW) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
     DUO_STAMP(2);
     u32x4_t xf[8];
-    auto ldx = [&](const lds_u8_t* sp, auto ks_c, auto b_c) {
-        constexpr int KS = decltype(ks_c)::value, B = decltype(b_c)::value;
-        const lds_u8_t* a = sp + (xbase ^ ((KS & 1) * 64));
-        return *reinterpret_cast<const lds_u32x4_t*>(a + (KS >> 1) * DHALF + B * 2048);
-    };
-    sfor<8>([&](auto bc) { xf[decltype(bc)::value] = ldx(smem, integral_constant<int, 0>{}, bc); });
+    sfor<8>([&](auto bc) { xf[decltype(bc)::value] = Duo::ldx<0, decltype(bc)::value>(smem, xbase); });
     for (int slab = 0; slab < nslab; ++slab) {
         const bool more = slab + 1 < nslab;
-        const unsigned char* ws = wstream + (size_t)slab * (DPS * 1024);
-        const unsigned char* wsn = wstream + (size_t)(more ? slab + 1 : 0) * (DPS * 1024);  // past the end: slab 0 again (never used)
+        const unsigned char* ws = wstream + (size_t)slab * (F1PS * 1024);
+        const unsigned char* wsn = wstream + (size_t)(more ? slab + 1 : 0) * (F1PS * 1024);  // past the end: slab 0 again (never used)
         const int ahead = slab + 2 < nslab ? slab + 2 : slab;  // (last two slabs: their own rows again, into the freed buffer)
-        const lds_u8_t* sp = smem + (slab & 1) * DSLAB;
-        const lds_u8_t* spn = smem + ((slab + 1) & 1) * DSLAB;
-
-        sfor<DPS>([&](auto pc) {
-            constexpr int P = decltype(pc)::value;
-            constexpr int KS = P >> 2, A = P & 3, SL = P % DRING;
-            fat_wait<SCHED::value.allowed[P]>(wr[SL]);
-            if constexpr (P == DBARRIER_AT) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-            }
-            sfor<8>([&](auto bc) {
-                constexpr int B = decltype(bc)::value;
-                if constexpr (!(DUO_ABL & 4)) fat_mfma<A * 8 + B>(wr[SL], xf[B]);
-                if constexpr (A == 3) {  // the next k-step's fragment replaces this one right behind its last reader
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (KS + 1 < 4) xf[B] = ldx(sp, integral_constant<int, KS + 1>{}, bc);
-                    else xf[B] = ldx(spn, integral_constant<int, 0>{}, bc);
-                }
-            });
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int Q = P + DRING;
-            if constexpr (!(DUO_ABL & 8)) {
-            if constexpr (Q >= DPS) issue_w(integral_constant<int, SL>{}, wsn, integral_constant<int, Q - DPS>{});
-            else issue_w(integral_constant<int, SL>{}, ws, integral_constant<int, Q>{});
-            }
-            if constexpr (!(DUO_ABL & 16))
-            sfor<dpieces_at(P)>([&](auto ic) { stage_piece(ahead, slab & 1, integral_constant<int, dpiece_first(P) + decltype(ic)::value>{}); });
-        });
+        const lds_u8_t* sp = smem + (slab & 1) * Duo::SLAB;
+        const lds_u8_t* spn = smem + ((slab + 1) & 1) * Duo::SLAB;
+        Duo::slab<DUO_F1ABL>(wr, xf, sp, spn, xbase, ws, wsn, lane16, [&](auto ic) { stage_piece(ahead, slab & 1, ic); });
     }
     DUO_STAMP(3);
-    // fragments and pieces requested past the end are still landing
+    // fragments and pieces requested past the end are still landing. (fat_ring_drain's text, inline: through the helper hipcc moved two
+    // scalar shifts of the epilogue's addressing behind the wait, and conv1x1_duo_kernel<0, 0> measured 0.55 us, 1 %, slower)
 #pragma unroll
-    for (int i = 0; i < DRING; ++i) asm volatile("" : "+v"(wr[i]));
+    for (int i = 0; i < F1RING; ++i) asm volatile("" : "+v"(wr[i]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < DRING; ++i) asm volatile("" : "+v"(wr[i]));
+    for (int i = 0; i < F1RING; ++i) asm volatile("" : "+v"(wr[i]));
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
 
     // ---- epilogue: + bias, + residual, ReLU, round once -- through a wave-private 16 KB LDS image of the wave's 128 rows x 128 B
@@ -289,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
     auto row_off = [&](int i) {  // piece i = rows 8 i + lrow: byte offset of this lane's 16 bytes (chunk lchk ^ swizzle(row)) in res / out
         const int row = 8 * i + lrow;
         const int gm = min(m0 + row, p.M - 1);
-        return (size_t)gm * p.Cout * 2 + colb + (size_t)((lchk ^ ((row >> 1) & 7)) << 4);
+        return (size_t)gm * p.Cout * 2 + colb + (size_t)Duo::swz(row, lchk);
     };
     const int cb = nt * 256 + wave * 64 + 8 * fchunk;
     const float alpha = p.alpha;
@@ -316,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
         auto row_off3 = [&](int i) {  // piece i = rows 8 i + lrow of the TILE: byte offset of this lane's 16 bytes in plane 0 of res / out
             const int row = 8 * i + lrow_e;
             const int gm = min(m0 + row, p.M - 1);
-            return (size_t)gm * ld3 + colb + (size_t)((lchk_e ^ ((row >> 1) & 7)) << 4);
+            return (size_t)gm * ld3 + colb + (size_t)Duo::swz(row, lchk_e);
         };
         sfor<2>([&](auto hc) {
             constexpr int h = decltype(hc)::value;
@@ -346,9 +305,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
                 const float4 b1 = *reinterpret_cast<const float4*>(p.bias + cb + 32 * j + 4);
                 sfor<4>([&](auto bc) {
                     constexpr int BL = decltype(bc)::value, B = 4 * h + BL;
-                    const f32x4_t lo = fat_read<(2 * j) * 8 + B>(), hi = fat_read<(2 * j + 1) * 8 + B>();
-                    float v[8] = {fmaf(alpha, lo[0], b0.x), fmaf(alpha, lo[1], b0.y), fmaf(alpha, lo[2], b0.z), fmaf(alpha, lo[3], b0.w),
-                                  fmaf(alpha, hi[0], b1.x), fmaf(alpha, hi[1], b1.y), fmaf(alpha, hi[2], b1.z), fmaf(alpha, hi[3], b1.w)};
+                    float v[8];
+                    fat_bias8<(2 * j) * 8 + B, (2 * j + 1) * 8 + B>(v, alpha, b0, b1);
                     lds_u32x4_t* const cell_h = reinterpret_cast<lds_u32x4_t*>(wt + (xbase ^ (j * 64)) + BL * 2048);  // row 16 BL + frow of this pass
                     lds_u32x4_t* const cell_l = reinterpret_cast<lds_u32x4_t*>(wt + 8192 + (xbase ^ (j * 64)) + BL * 2048);
                     if (has_res) {
@@ -371,23 +329,14 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
                             }
                         }
                     }
-                    if (p.relu) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-                    }
+                    fat_relu8(v, p.relu);
                     if constexpr (!POOL) {   // (the pooled plane form never writes the map: agrl_conv1x1_split16_pool passes no out)
-                      if (has_out) {
-                        uint32_t ph[4], pl[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            ph[e] = pack_lp16x2(v[2 * e], v[2 * e + 1]);
-                            float a0, a1;
-                            unpack_lp16x2(ph[e], a0, a1);
-                            pl[e] = pack_lp16x2((v[2 * e] - a0) * 2048.f, (v[2 * e + 1] - a1) * 2048.f);
+                        if (has_out) {
+                            uint4 ph, pl;
+                            split16_pack8(v, ph, pl);
+                            *cell_h = u32x4_t{ph.x, ph.y, ph.z, ph.w};
+                            *cell_l = u32x4_t{pl.x, pl.y, pl.z, pl.w};
                         }
-                        *cell_h = u32x4_t{ph[0], ph[1], ph[2], ph[3]};
-                        *cell_l = u32x4_t{pl[0], pl[1], pl[2], pl[3]};
-                      }
                     }
                     if constexpr (POOL) {
 #pragma unroll
@@ -409,24 +358,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
                     }
                 }
             }
-            if constexpr (POOL) {   // sum over the 16 pixel lanes of a fragment (same f), park the quarter sums (igemm_wide_kernel<16384>'s order)
+            if constexpr (POOL) {
                 float* const s_w = s_pool_ + wave * 256;
 #pragma unroll
                 for (int q = 0; q < 2; ++q)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            float t = ps[q][j][e];
-                            t += __shfl_xor(t, 1, 64); t += __shfl_xor(t, 2, 64); t += __shfl_xor(t, 4, 64); t += __shfl_xor(t, 8, 64);
-                            ps[q][j][e] = t;
-                        }
-                        if (frow == 0) {
-                            float* d = s_w + (2 * h + q) * 64 + 8 * fchunk + 32 * j;
-                            *reinterpret_cast<float4*>(d) = make_float4(ps[q][j][0], ps[q][j][1], ps[q][j][2], ps[q][j][3]);
-                            *reinterpret_cast<float4*>(d + 4) = make_float4(ps[q][j][4], ps[q][j][5], ps[q][j][6], ps[q][j][7]);
-                        }
-                    }
+                    for (int j = 0; j < 2; ++j) duo_quarter_park(ps[q][j], frow, s_w + (2 * h + q) * 64 + 8 * fchunk + 32 * j);
             }
             // the image is re-filled by the next pass's DMA: every LDS read of this pass must have returned first
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -444,37 +381,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
         const float4 b1 = *reinterpret_cast<const float4*>(p.bias + cb + 32 * j + 4);
         sfor<8>([&](auto bc) {
             constexpr int B = decltype(bc)::value;
-            const f32x4_t lo = fat_read<(2 * j) * 8 + B>(), hi = fat_read<(2 * j + 1) * 8 + B>();
-            float v[8] = {fmaf(alpha, lo[0], b0.x), fmaf(alpha, lo[1], b0.y), fmaf(alpha, lo[2], b0.z), fmaf(alpha, lo[3], b0.w),
-                          fmaf(alpha, hi[0], b1.x), fmaf(alpha, hi[1], b1.y), fmaf(alpha, hi[2], b1.z), fmaf(alpha, hi[3], b1.w)};   // (alpha = 1: acc + b bit for bit)
             lds_u32x4_t* const cell = reinterpret_cast<lds_u32x4_t*>(wt + (xbase ^ (j * 64)) + B * 2048);  // row 16 B + frow, chunk 4 j + f
-            if (has_res) {
-                const u32x4_t r = *cell;
-                const uint32_t w4[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float l, h;
-                    unpack_lp16x2(w4[e], l, h);
-                    v[2 * e] += l;
-                    v[2 * e + 1] += h;
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-            }
-            const u32x4_t pk = {pack_lp16x2(v[0], v[1]), pack_lp16x2(v[2], v[3]), pack_lp16x2(v[4], v[5]), pack_lp16x2(v[6], v[7])};
-            if (has_out) *cell = pk;
-            if constexpr (POOL) {  // pool the rounded activations (what a separate pooling pass would read)
-                const uint32_t w4[4] = {pk.x, pk.y, pk.z, pk.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float l, h;
-                    unpack_lp16x2(w4[e], l, h);
-                    psum[B >> 1][j][2 * e] += l;
-                    psum[B >> 1][j][2 * e + 1] += h;
-                }
-            }
+            duo_combine<(2 * j) * 8 + B, (2 * j + 1) * 8 + B, POOL>(cell, alpha, b0, b1, has_res, p.relu, has_out, psum[POOL ? B >> 1 : 0][j]);
         });
     });
     DUO_STAMP(6);
@@ -500,19 +408,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float t = psum[q][j][e];
-                    t += __shfl_xor(t, 1, 64); t += __shfl_xor(t, 2, 64); t += __shfl_xor(t, 4, 64); t += __shfl_xor(t, 8, 64);
-                    psum[q][j][e] = t;
-                }
-                if (frow == 0) {
-                    float* d = s_w + q * 64 + 8 * fchunk + 32 * j;
-                    *reinterpret_cast<float4*>(d) = make_float4(psum[q][j][0], psum[q][j][1], psum[q][j][2], psum[q][j][3]);
-                    *reinterpret_cast<float4*>(d + 4) = make_float4(psum[q][j][4], psum[q][j][5], psum[q][j][6], psum[q][j][7]);
-                }
-            }
+            for (int j = 0; j < 2; ++j) duo_quarter_park(psum[q][j], frow, s_w + q * 64 + 8 * fchunk + 32 * j);
         }
         __syncthreads();
         const int P = p.pool_nparts;
@@ -541,9 +437,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_kernel(const DuoParams p) 
 // only ever meets MORE already-retired operations in this order, never fewer.
 template <bool POOL>
 __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoParams p, int ntiles) {
-    using SCHED = DuoSchedOf;
     using std::integral_constant;
-    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * DSLAB];
+    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * Duo::SLAB];
     __shared__ __attribute__((aligned(16))) float s_pool_[POOL ? 4 * 256 : 4];
     lds_u8_t* const smem = (lds_u8_t*)smem_;
     const unsigned lds0 = (unsigned)(size_t)smem;
@@ -559,9 +454,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
 
     // virtual block id -> tile, the one-shot form's XCD map over ALL tiles (gridDim.x is a multiple of 8: a workgroup's tiles keep its XCD)
     auto tile_of = [&](int vb, int& mt_, int& nt_) {
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int xcd = vb & 7, within = vb >> 3;
-        const int b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
+        const int b = fat_xcd_tile(vb, ntiles);
         mt_ = b / nNt;
         nt_ = b - mt_ * nNt;
     };
@@ -572,7 +465,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
         // sites, so that hipcc recomputes the row terms there instead of carrying them through the k-loop: the kernel sits at its 128 arch VGPRs)
         const int row = (wave + 4 * j) * 8 + lrow_;
         const int gm = min(m0_ + row, p.M - 1);
-        const unsigned sw = (unsigned)((lchk_ ^ ((row >> 1) & 7)) << 4);
+        const unsigned sw = Duo::swz(row, lchk_);
         if (second) return (unsigned)gm * (unsigned)(p.K - p.K1) * 2u + sw;
         unsigned srow = (unsigned)gm;
         if (p.gHoWo) {
@@ -584,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
     };
     int vb = blockIdx.x, mt, nt;
     tile_of(vb, mt, nt);
-    int m0 = mt * DROWS;
+    int m0 = mt * Duo::ROWS;
     unsigned roff[4], roff2[4], roffd[4];   // roffd: next tile's source-1 offsets minus this tile's
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -600,37 +493,28 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
         const unsigned ro1 = roff[J] + (nx ? roffd[J] : 0u);
         const unsigned char* src = second ? p.x2 + roff2[J] + (size_t)((slab - nslab1) * 256 + H * 128)
                                           : p.x + ro1 + (size_t)(slab * 256 + H * 128);
-        fat_dma(src, __builtin_amdgcn_readfirstlane(lds0 + buf * DSLAB + H * DHALF + (wave + 4 * J) * 1024));
+        Duo::stage<I>(src, lds0, buf, wave);
     };
-    const int xbase = frow * 128 + ((fchunk ^ ((frow >> 1) & 7)) << 4);
-    auto stream_of = [&](int nt_) { return p.wpk + (size_t)(nt_ * 4 + wave) * nslab * (DPS * 1024); };
+    const int xbase = Duo::xbase(frow, fchunk);
+    auto stream_of = [&](int nt_) { return p.wpk + (size_t)(nt_ * 4 + wave) * nslab * (F1PS * 1024); };
     const unsigned char* wstream = stream_of(nt);
-    u32x4_t wr[DRING];
-    auto issue_w = [&](auto slot_c, const unsigned char* slab_base, auto pos_c) {
-        constexpr int SLOT = decltype(slot_c)::value, POS = decltype(pos_c)::value;
-        fat_gload<(POS & 3) * 1024>(wr[SLOT], lane16, slab_base + (POS & ~3) * 1024);
-    };
+    u32x4_t wr[F1RING];
     asm volatile("" ::: "a127");
 
     // ---- prologue of the FIRST tile (the one-shot form's)
-    sfor<DPPW>([&](auto ic) { stage_piece(0, 0, ic, false); });
-    sfor<DRING>([&](auto ic) {
+    sfor<Duo::PPW>([&](auto ic) { stage_piece(0, 0, ic, false); });
+    sfor<F1RING>([&](auto ic) {
         constexpr int I = decltype(ic)::value;
-        issue_w(ic, wstream, ic);
-        sfor<dpieces_at(I + DRING)>([&](auto jc) {
-            stage_piece(1, 1, integral_constant<int, dpiece_first(I + DRING) + decltype(jc)::value>{}, false);
+        Duo::issue_w<I>(wr[I], lane16, wstream);
+        sfor<Duo::pieces_at(I + F1RING)>([&](auto jc) {
+            stage_piece(1, 1, integral_constant<int, Duo::piece_first(I + F1RING) + decltype(jc)::value>{}, false);
         });
     });
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DRING + DPPW) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1RING + Duo::PPW) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
     int par = 0;   // buffer of the current tile's slab 0
-    auto ldx = [&](const lds_u8_t* sp, auto ks_c, auto b_c) {
-        constexpr int KS = decltype(ks_c)::value, B = decltype(b_c)::value;
-        const lds_u8_t* a = sp + (xbase ^ ((KS & 1) * 64));
-        return *reinterpret_cast<const lds_u32x4_t*>(a + (KS >> 1) * DHALF + B * 2048);
-    };
     const bool has_res = p.res != nullptr;
     const bool has_out = !POOL || p.out != nullptr;
     const float alpha = p.alpha;
@@ -645,58 +529,29 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
             int lr = lrow, lc = lchk;
             asm volatile("" : "+v"(lr), "+v"(lc));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) roffd[j] = roff_of(mtn * DROWS, j, false, lr, lc) - roff[j];
+            for (int j = 0; j < 4; ++j) roffd[j] = roff_of(mtn * Duo::ROWS, j, false, lr, lc) - roff[j];
             wstream_n = stream_of(ntn);
         }
         u32x4_t xf[8];
-        sfor<8>([&](auto bc) { xf[decltype(bc)::value] = ldx(smem + par * DSLAB, integral_constant<int, 0>{}, bc); });
+        sfor<8>([&](auto bc) { xf[decltype(bc)::value] = Duo::ldx<0, decltype(bc)::value>(smem + par * Duo::SLAB, xbase); });
         for (int slab = 0; slab < nslab; ++slab) {
             const bool more = slab + 1 < nslab;
-            const unsigned char* ws = wstream + (size_t)slab * (DPS * 1024);
-            const unsigned char* wsn = more ? wstream + (size_t)(slab + 1) * (DPS * 1024) : wstream_n;   // last slab: the NEXT tile's first ring
+            const unsigned char* ws = wstream + (size_t)slab * (F1PS * 1024);
+            const unsigned char* wsn = more ? wstream + (size_t)(slab + 1) * (F1PS * 1024) : wstream_n;   // last slab: the NEXT tile's first ring
             const bool nx = has_next && slab + 2 == nslab;                   // second-last slab: the next tile's slab 0 ...
             const int ahead = nx ? 0 : (slab + 2 < nslab ? slab + 2 : slab);  // ... (last slab, last tile: dummies -- the slab's own rows again)
             const int cur = (slab + par) & 1;
-            const lds_u8_t* sp = smem + cur * DSLAB;
-            const lds_u8_t* spn = smem + (cur ^ 1) * DSLAB;
-            sfor<DPS>([&](auto pc) {
-                constexpr int P = decltype(pc)::value;
-                constexpr int KS = P >> 2, A = P & 3, SL = P % DRING;
-                fat_wait<SCHED::value.allowed[P]>(wr[SL]);
-                if constexpr (P == DBARRIER_AT) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                }
-                sfor<8>([&](auto bc) {
-                    constexpr int B = decltype(bc)::value;
-                    fat_mfma<A * 8 + B>(wr[SL], xf[B]);
-                    if constexpr (A == 3) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (KS + 1 < 4) xf[B] = ldx(sp, integral_constant<int, KS + 1>{}, bc);
-                        else xf[B] = ldx(spn, integral_constant<int, 0>{}, bc);
-                    }
-                });
-                __builtin_amdgcn_sched_barrier(0);
-                constexpr int Q = P + DRING;
-                if constexpr (Q >= DPS) issue_w(integral_constant<int, SL>{}, wsn, integral_constant<int, Q - DPS>{});
-                else issue_w(integral_constant<int, SL>{}, ws, integral_constant<int, Q>{});
-                sfor<dpieces_at(P)>([&](auto ic) { stage_piece(ahead, cur, integral_constant<int, dpiece_first(P) + decltype(ic)::value>{}, nx); });
-            });
+            const lds_u8_t* sp = smem + cur * Duo::SLAB;
+            const lds_u8_t* spn = smem + (cur ^ 1) * Duo::SLAB;
+            Duo::slab<0>(wr, xf, sp, spn, xbase, ws, wsn, lane16, [&](auto ic) { stage_piece(ahead, cur, ic, nx); });
         }
-        // the next tile's first ring and its slab 0 (or the dummies of the last tile) are still landing
-#pragma unroll
-        for (int i = 0; i < DRING; ++i) asm volatile("" : "+v"(wr[i]));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < DRING; ++i) asm volatile("" : "+v"(wr[i]));
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+        fat_ring_drain(wr);   // the next tile's first ring and its slab 0 (or the dummies of the last tile) are still landing
         __syncthreads();  // every wave is past its last fragment read of the LAST slab's buffer: it becomes the image area
 
         // ---- epilogue in the last slab's buffer: wave image 8 KB = 64 rows x 128 B (the pixel buffers' swizzled row layout), two passes
         const int bufE = (nslab - 1 + par) & 1;
-        lds_u8_t* const wt = smem + bufE * DSLAB + wave * 8192;
-        const unsigned ldsE = lds0 + bufE * DSLAB + wave * 8192;
+        lds_u8_t* const wt = smem + bufE * Duo::SLAB + wave * 8192;
+        const unsigned ldsE = lds0 + bufE * Duo::SLAB + wave * 8192;
         const size_t colb = (size_t)(nt * 256 + wave * 64) * 2;
         const int cb = nt * 256 + wave * 64 + 8 * fchunk;
         int lrow_e = lrow, lchk_e = lchk;
@@ -704,7 +559,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
         auto row_off = [&](int i) {
             const int row = 8 * i + lrow_e;
             const int gm = min(m0 + row, p.M - 1);
-            return (unsigned)((size_t)gm * p.Cout * 2 + colb + (size_t)((lchk_e ^ ((row >> 1) & 7)) << 4));
+            return (unsigned)((size_t)gm * p.Cout * 2 + colb + (size_t)Duo::swz(row, lchk_e));
         };
         sfor<2>([&](auto hc) {
             constexpr int h = decltype(hc)::value;
@@ -728,37 +583,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
                 const float4 b1 = *reinterpret_cast<const float4*>(p.bias + cb + 32 * j + 4);
                 sfor<4>([&](auto bc) {
                     constexpr int BL = decltype(bc)::value, B = 4 * h + BL;
-                    const f32x4_t lo = fat_read<(2 * j) * 8 + B>(), hi = fat_read<(2 * j + 1) * 8 + B>();
-                    float v[8] = {fmaf(alpha, lo[0], b0.x), fmaf(alpha, lo[1], b0.y), fmaf(alpha, lo[2], b0.z), fmaf(alpha, lo[3], b0.w),
-                                  fmaf(alpha, hi[0], b1.x), fmaf(alpha, hi[1], b1.y), fmaf(alpha, hi[2], b1.z), fmaf(alpha, hi[3], b1.w)};
                     lds_u32x4_t* const cell = reinterpret_cast<lds_u32x4_t*>(wt + (xbase ^ (j * 64)) + BL * 2048);
-                    if (has_res) {
-                        const u32x4_t r = *cell;
-                        const uint32_t w4[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float l, hh;
-                            unpack_lp16x2(w4[e], l, hh);
-                            v[2 * e] += l;
-                            v[2 * e + 1] += hh;
-                        }
-                    }
-                    if (p.relu) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-                    }
-                    const u32x4_t pk = {pack_lp16x2(v[0], v[1]), pack_lp16x2(v[2], v[3]), pack_lp16x2(v[4], v[5]), pack_lp16x2(v[6], v[7])};
-                    if (has_out) *cell = pk;
-                    if constexpr (POOL) {  // pool the rounded activations (what a separate pooling pass would read)
-                        const uint32_t w4[4] = {pk.x, pk.y, pk.z, pk.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float l, hh;
-                            unpack_lp16x2(w4[e], l, hh);
-                            ps[BL >> 1][j][2 * e] += l;
-                            ps[BL >> 1][j][2 * e + 1] += hh;
-                        }
-                    }
+                    duo_combine<(2 * j) * 8 + B, (2 * j + 1) * 8 + B, POOL>(cell, alpha, b0, b1, has_res, p.relu, has_out, ps[POOL ? BL >> 1 : 0][j]);
                 });
             });
             if (has_out) {
@@ -773,19 +599,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
 #pragma unroll
                 for (int q = 0; q < 2; ++q)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            float t = ps[q][j][e];
-                            t += __shfl_xor(t, 1, 64); t += __shfl_xor(t, 2, 64); t += __shfl_xor(t, 4, 64); t += __shfl_xor(t, 8, 64);
-                            ps[q][j][e] = t;
-                        }
-                        if (frow == 0) {
-                            float* d = s_w + (2 * h + q) * 64 + 8 * fchunk + 32 * j;
-                            *reinterpret_cast<float4*>(d) = make_float4(ps[q][j][0], ps[q][j][1], ps[q][j][2], ps[q][j][3]);
-                            *reinterpret_cast<float4*>(d + 4) = make_float4(ps[q][j][4], ps[q][j][5], ps[q][j][6], ps[q][j][7]);
-                        }
-                    }
+                    for (int j = 0; j < 2; ++j) duo_quarter_park(ps[q][j], frow, s_w + (2 * h + q) * 64 + 8 * fchunk + 32 * j);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the image is re-filled by the next pass's DMA
         });
@@ -807,7 +621,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
         // ---- on to the next tile: its slab 0 sits in the other buffer, its first ring in wr[]; slab 1 goes where the images were
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();   // every wave has read its image rows (and the pooled sums): the buffer is free
-        vb = vbn; mt = mtn; nt = ntn; m0 = mt * DROWS;
+        vb = vbn; mt = mtn; nt = ntn; m0 = mt * Duo::ROWS;
         int lr2 = lrow, lc2 = lchk;
         asm volatile("" : "+v"(lr2), "+v"(lc2));
 #pragma unroll
@@ -817,13 +631,13 @@ __global__ __launch_bounds__(256, 2) void conv1x1_duo_persist_kernel(const DuoPa
         }
         wstream = wstream_n;
         par = (nslab + par) & 1;
-        sfor<DPPW>([&](auto ic) { stage_piece(nslab > 1 ? 1 : 0, par ^ 1, ic, false); });
+        sfor<Duo::PPW>([&](auto ic) { stage_piece(nslab > 1 ? 1 : 0, par ^ 1, ic, false); });
     }
 }
 
 int duo_launch(DuoParams& p, bool pool, hipStream_t stream, const char* who) {
     if (!p.planes) p.alpha = 1.f;   // the 16-bit entry points: acc + bias, bit for bit what round 5 computed
-    const int grid = ((p.M + DROWS - 1) / DROWS) * (p.Cout >> 8);
+    const int grid = ((p.M + Duo::ROWS - 1) / Duo::ROWS) * (p.Cout >> 8);
     constexpr int dyn = (DUO_ABL & 32) ? 48 * 1024 : 0;
     if (p.planes) {
         if (pool) hipLaunchKernelGGL((conv1x1_duo_kernel<true, true>), dim3(grid), dim3(256), dyn, stream, p);
@@ -850,21 +664,49 @@ extern "C" int agrl_duo_trace_buffer(void* buf) {  // profiling build only
 }
 #endif
 
-extern "C" int agrl_conv1x1_packed_res_bn_act(const void* x, const void* packed, const float* bias, const void* residual, void* out,
-                                              int M, int K, int Cout, int relu, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(x && packed && bias && out, "agrl_conv1x1_packed_res_bn_act: null pointer");
-    AGRL_CHECK_ARG(M > 0 && K > 0 && K % 128 == 0 && Cout > 0 && Cout % 256 == 0,
-                   "agrl_conv1x1_packed_res_bn_act: needs K %% 128 == 0 and Cout %% 256 == 0; got M=%d K=%d Cout=%d", M, K, Cout);
-    AGRL_CHECK_ARG((size_t)M * (size_t)(K > Cout ? K : Cout) * 2 < (1ull << 32), "agrl_conv1x1_packed_res_bn_act: maps beyond 4 GB are not addressed");
-    AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)out) & 15) == 0,
-                   "agrl_conv1x1_packed_res_bn_act: pointers must be 16-byte aligned");
-    DuoParams p{};
+// AdaptiveAvgPool2d bins over the H image rows of a frame for every split; here: whole quarters (4 rows) of the frame, at most 16 bins
+static int duo_pool_bins(DuoParams& p, const int* splits, int n_splits, int H, const char* who) {
+    int P = 0;
+    for (int i = 0; i < n_splits; ++i) {
+        const int n = splits[i];
+        AGRL_CHECK_ARG(n > 0 && P + n <= 16, "%s: at most 16 bins", who);
+        for (int j = 0; j < n; ++j) {
+            const int r0 = (j * H) / n, r1 = ((j + 1) * H + n - 1) / n;
+            AGRL_CHECK_ARG((r0 & 3) == 0 && (r1 & 3) == 0, "%s: bins must be made of whole 4-row quarters (split %d)", who, n);
+            p.pool_q0[P] = r0 >> 2;
+            p.pool_q1[P] = r1 >> 2;
+            ++P;
+        }
+    }
+    p.pool_nparts = P;
+    return 0;
+}
+
+// What the 16-bit entry points share: the null / divisibility / 4 GB / alignment checks and the DuoParams fill. x2, K2: the second source
+// (`dual`) or nullptr, 0; dst: the stored map or the pooled sums; M: rows of the GEMM; xrows: pixel rows of x (the strided form reads a
+// larger map than it writes).
+static int duo_common(DuoParams& p, const char* who, const void* x, const void* x2, bool dual, const void* packed, const float* bias,
+                      const void* residual, const void* dst, long long M, size_t xrows, int K1, int K2, int Cout, int relu) {
+    AGRL_CHECK_ARG(x && packed && bias && dst && (x2 || !dual), "%s: null pointer", who);
+    AGRL_CHECK_ARG(M > 0 && K1 > 0 && K1 % 128 == 0 && (dual ? K2 > 0 : K2 == 0) && K2 % 128 == 0 && Cout > 0 && Cout % 256 == 0,
+                   "%s: needs K %% 128 == 0 (of each source) and Cout %% 256 == 0; got M=%lld K1=%d K2=%d Cout=%d", who, M, K1, K2, Cout);
+    AGRL_CHECK_ARG(xrows * K1 * 2 < (1ull << 32) && (size_t)M * (size_t)(Cout > K2 ? Cout : K2) * 2 < (1ull << 32), "%s: maps beyond 4 GB are not addressed", who);
+    AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)dst) & 15) == 0,
+                   "%s: pointers must be 16-byte aligned", who);
     p.x = reinterpret_cast<const unsigned char*>(x);
+    p.x2 = reinterpret_cast<const unsigned char*>(x2);
     p.wpk = reinterpret_cast<const unsigned char*>(packed);
     p.bias = bias;
     p.res = reinterpret_cast<const unsigned char*>(residual);
+    p.M = (int)M; p.K = K1 + K2; p.K1 = K1; p.Cout = Cout; p.relu = relu;
+    return 0;
+}
+
+extern "C" int agrl_conv1x1_packed_res_bn_act(const void* x, const void* packed, const float* bias, const void* residual, void* out,
+                                              int M, int K, int Cout, int relu, agrl_stream_t stream) {
+    DuoParams p{};
+    if (int rc = duo_common(p, "agrl_conv1x1_packed_res_bn_act", x, nullptr, false, packed, bias, residual, out, M, (size_t)M, K, 0, Cout, relu)) return rc;
     p.out = reinterpret_cast<unsigned char*>(out);
-    p.M = M; p.K = K; p.K1 = K; p.Cout = Cout; p.relu = relu;
     return duo_launch(p, false, (hipStream_t)stream, "agrl_conv1x1_packed_res_bn_act");
 }
 
@@ -873,52 +715,20 @@ extern "C" int agrl_conv1x1_packed_res_pool(const void* x, const void* packed, c
                                             const int* splits, int n_splits, int mean, agrl_stream_t stream) {
     AGRL_CHECK_ARG(x && packed && bias && pool_out && splits, "agrl_conv1x1_packed_res_pool: null pointer");
     AGRL_CHECK_ARG(H == 16 && W == 8, "agrl_conv1x1_packed_res_pool: a frame must be 16 x 8 pixels (got %dx%d)", H, W);
-    AGRL_CHECK_ARG(N > 0 && K > 0 && K % 128 == 0 && Cout > 0 && Cout % 256 == 0,
-                   "agrl_conv1x1_packed_res_pool: needs K %% 128 == 0 and Cout %% 256 == 0; got N=%d K=%d Cout=%d", N, K, Cout);
-    AGRL_CHECK_ARG((size_t)N * 128 * (size_t)(K > Cout ? K : Cout) * 2 < (1ull << 32), "agrl_conv1x1_packed_res_pool: maps beyond 4 GB are not addressed");
-    AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)pool_out) & 15) == 0,
-                   "agrl_conv1x1_packed_res_pool: pointers must be 16-byte aligned");
     DuoParams p{};
-    int P = 0;
-    for (int i = 0; i < n_splits; ++i) {
-        const int n = splits[i];
-        AGRL_CHECK_ARG(n > 0 && P + n <= 16, "agrl_conv1x1_packed_res_pool: at most 16 bins");
-        for (int j = 0; j < n; ++j) {  // AdaptiveAvgPool2d bins over image rows; here: whole quarters of the frame
-            const int r0 = (j * H) / n, r1 = ((j + 1) * H + n - 1) / n;
-            AGRL_CHECK_ARG((r0 & 3) == 0 && (r1 & 3) == 0, "agrl_conv1x1_packed_res_pool: bins must be made of whole 4-row quarters (split %d)", n);
-            p.pool_q0[P] = r0 >> 2;
-            p.pool_q1[P] = r1 >> 2;
-            ++P;
-        }
-    }
-    p.pool_nparts = P; p.pool_mean = mean;
+    if (int rc = duo_common(p, "agrl_conv1x1_packed_res_pool", x, nullptr, false, packed, bias, residual, pool_out, (long long)N * 128, (size_t)N * 128, K, 0, Cout, relu)) return rc;
+    if (int rc = duo_pool_bins(p, splits, n_splits, H, "agrl_conv1x1_packed_res_pool")) return rc;
+    p.pool_mean = mean;
     p.pool_out = pool_out;
     p.pool_out_lp = reinterpret_cast<unsigned short*>(pool_out_lp);
-    p.x = reinterpret_cast<const unsigned char*>(x);
-    p.wpk = reinterpret_cast<const unsigned char*>(packed);
-    p.bias = bias;
-    p.res = reinterpret_cast<const unsigned char*>(residual);
-    p.out = nullptr;
-    p.M = N * 128; p.K = K; p.K1 = K; p.Cout = Cout; p.relu = relu;
     return duo_launch(p, true, (hipStream_t)stream, "agrl_conv1x1_packed_res_pool");
 }
 
 extern "C" int agrl_conv1x1_packed_dual_duo(const void* x, const void* x2, const void* packed, const float* bias, void* out, int M, int K1,
                                             int K2, int Cout, int relu, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(x && x2 && packed && bias && out, "agrl_conv1x1_packed_dual_duo: null pointer");
-    AGRL_CHECK_ARG(M > 0 && K1 > 0 && K1 % 128 == 0 && K2 > 0 && K2 % 128 == 0 && Cout > 0 && Cout % 256 == 0,
-                   "agrl_conv1x1_packed_dual_duo: needs K1, K2 %% 128 == 0 and Cout %% 256 == 0; got M=%d K1=%d K2=%d Cout=%d", M, K1, K2, Cout);
-    const size_t widest = (size_t)(K1 > Cout ? (K1 > K2 ? K1 : K2) : (Cout > K2 ? Cout : K2));
-    AGRL_CHECK_ARG((size_t)M * widest * 2 < (1ull << 32), "agrl_conv1x1_packed_dual_duo: maps beyond 4 GB are not addressed");
-    AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)out) & 15) == 0,
-                   "agrl_conv1x1_packed_dual_duo: pointers must be 16-byte aligned");
     DuoParams p{};
-    p.x = reinterpret_cast<const unsigned char*>(x);
-    p.x2 = reinterpret_cast<const unsigned char*>(x2);
-    p.wpk = reinterpret_cast<const unsigned char*>(packed);
-    p.bias = bias;
+    if (int rc = duo_common(p, "agrl_conv1x1_packed_dual_duo", x, x2, true, packed, bias, nullptr, out, M, (size_t)M, K1, K2, Cout, relu)) return rc;
     p.out = reinterpret_cast<unsigned char*>(out);
-    p.M = M; p.K = K1 + K2; p.K1 = K1; p.Cout = Cout; p.relu = relu;
     return duo_launch(p, false, (hipStream_t)stream, "agrl_conv1x1_packed_dual_duo");
 }
 
@@ -930,21 +740,10 @@ extern "C" int agrl_conv1x1_packed_dual_strided(const void* x, const void* x2, c
                                                 int Hi, int Wi, int stride, int K1, int K2, int Cout, int relu, agrl_stream_t stream) {
     AGRL_CHECK_ARG(x && x2 && packed && bias && out, "agrl_conv1x1_packed_dual_strided: null pointer");
     AGRL_CHECK_ARG(N > 0 && Hi > 0 && Wi > 0 && stride >= 1, "agrl_conv1x1_packed_dual_strided: bad map %dx%dx%d stride %d", N, Hi, Wi, stride);
-    AGRL_CHECK_ARG(K1 > 0 && K1 % 128 == 0 && K2 > 0 && K2 % 128 == 0 && Cout > 0 && Cout % 256 == 0,
-                   "agrl_conv1x1_packed_dual_strided: needs K1, K2 %% 128 == 0 and Cout %% 256 == 0; got K1=%d K2=%d Cout=%d", K1, K2, Cout);
     const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    const size_t M = (size_t)N * Ho * Wo;
-    AGRL_CHECK_ARG((size_t)N * Hi * Wi * K1 * 2 < (1ull << 32) && M * (size_t)(Cout > K2 ? Cout : K2) * 2 < (1ull << 32),
-                   "agrl_conv1x1_packed_dual_strided: maps beyond 4 GB are not addressed");
-    AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)out) & 15) == 0,
-                   "agrl_conv1x1_packed_dual_strided: pointers must be 16-byte aligned");
     DuoParams p{};
-    p.x = reinterpret_cast<const unsigned char*>(x);
-    p.x2 = reinterpret_cast<const unsigned char*>(x2);
-    p.wpk = reinterpret_cast<const unsigned char*>(packed);
-    p.bias = bias;
+    if (int rc = duo_common(p, "agrl_conv1x1_packed_dual_strided", x, x2, true, packed, bias, nullptr, out, (long long)N * Ho * Wo, (size_t)N * Hi * Wi, K1, K2, Cout, relu)) return rc;
     p.out = reinterpret_cast<unsigned char*>(out);
-    p.M = (int)M; p.K = K1 + K2; p.K1 = K1; p.Cout = Cout; p.relu = relu;
     if (stride > 1) { p.gHoWo = Ho * Wo; p.gWo = Wo; p.gS = stride; p.gWi = Wi; p.gHiWi = Hi * Wi; }
     return duo_launch(p, false, (hipStream_t)stream, "agrl_conv1x1_packed_dual_strided");
 }
@@ -1002,19 +801,8 @@ extern "C" int agrl_conv1x1_split16_pool(const void* x, const void* packed, cons
     AGRL_CHECK_ARG(H == 16 && W == 8 && N > 0, "agrl_conv1x1_split16_pool: a frame must be 16 x 8 pixels (got %dx%d)", H, W);
     if (int rc = duo_split16_common(p, x, packed, bias, N * 128, K3, Cout, relu, w_unscale, layout, "agrl_conv1x1_split16_pool")) return rc;
     AGRL_CHECK_ARG((((uintptr_t)x | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)pool_out) & 15) == 0, "agrl_conv1x1_split16_pool: pointers must be 16-byte aligned");
-    int P = 0;
-    for (int i = 0; i < n_splits; ++i) {
-        const int n = splits[i];
-        AGRL_CHECK_ARG(n > 0 && P + n <= 16, "agrl_conv1x1_split16_pool: at most 16 bins");
-        for (int j = 0; j < n; ++j) {
-            const int r0 = (j * H) / n, r1 = ((j + 1) * H + n - 1) / n;
-            AGRL_CHECK_ARG((r0 & 3) == 0 && (r1 & 3) == 0, "agrl_conv1x1_split16_pool: bins must be made of whole 4-row quarters (split %d)", n);
-            p.pool_q0[P] = r0 >> 2;
-            p.pool_q1[P] = r1 >> 2;
-            ++P;
-        }
-    }
-    p.pool_nparts = P; p.pool_mean = mean;
+    if (int rc = duo_pool_bins(p, splits, n_splits, H, "agrl_conv1x1_split16_pool")) return rc;
+    p.pool_mean = mean;
     p.pool_out = pool_out;
     p.pool_out_lp = nullptr;
     p.res = reinterpret_cast<const unsigned char*>(residual);

@@ -12,7 +12,7 @@
 //   * LDS holds the pixel rows of the current and the next 128-channel slab (2 x 64 KB; two 64-channel halves of 256 rows x 128 B
 //     in igemm_kernel's swizzled row layout), LDS-DMA in 1-KiB pieces behind the slab's first weight fragments; a k-step's 16 pixel fragments are read
 //     once per wave and held while its four weight fragments pass, each replaced by its successor behind its last reader;
-//   * one barrier per slab (256 MFMAs per wave), placed where no wave has to wait for LDS data behind it (see BARRIER_AT).
+//   * one barrier per slab (256 MFMAs per wave), placed where no wave has to wait for LDS data behind it (F1BARRIER_AT, fat1x1_dev.h).
 // M need not be a tile multiple: rows beyond M are staged from row M - 1 and not stored.
 //
 // Measured (rocprofv3 kernel durations, 256 frames of 16 x 8, fp16, tools/kernel_trace.sh tools/conv1x1_bench.py), this kernel /
@@ -42,7 +42,7 @@
 // Four designs for conv3 + residual of layer 4 (8-wave LDS ring, this kernel with the residual as slabs / in registers /
 // persistent, the back-to-back seam kernel) land within 5 % of each other at 2.6 TB/s of HBM traffic: 300 MB per launch, half of
 // it written, with 33 MB of operand rows re-read through L2 by eight channel tiles.
-#include "fat_dev.h"
+#include "fat1x1_dev.h"
 
 namespace {
 
@@ -58,47 +58,12 @@ struct Fat1Params {
 #ifndef FAT1_ABL
 #define FAT1_ABL 0  // timing ablations (results wrong): 1 no weight loads in the loop, 2 no pixel DMA in the loop, 4 no LDS reads in the loop
 #endif
-constexpr int F1RING = 8;                // weight fragments in flight per wave
-constexpr int F1PS = 4 * 4;              // weight fragments per 128-channel slab and wave: 4 k-steps x 4 channel fragments
-constexpr int HALF_BYTES = 256 * 128;    // 256 pixel rows x 64 channels
-constexpr int SLAB1 = 2 * HALF_BYTES;    // one 128-channel slab of the pixel tile
-constexpr int PPW1 = 16;                 // DMA pieces (8 rows x 128 B) per wave and slab
-// Slab s is read during the weight fragments 0 .. 15 of slab s -- its LAST k-step's pixel fragments behind fragment 11 -- and the
-// first k-step of slab s + 1 behind fragment 15. One barrier per slab, in front of fragment 12: there every wave has issued (and
-// waited out) its last reads of slab s's buffer and has waited for its own pieces of slab s + 1 (requested behind fragments
-// 12 .. 15 of slab s - 1, i.e. older than the weight fragments it has consumed since), so behind the barrier (a) slab s + 1 is
-// complete for everybody and (b) slab s's buffer is free: the pieces of slab s + 2 go into it behind fragments 12 .. 15, four each.
-// No wave ever waits for LDS data at a slab boundary.
-constexpr int BARRIER_AT = 12;
-constexpr int pieces_at(int p) { return p >= BARRIER_AT ? 4 : 0; }
-constexpr int piece_first(int p) { int n = 0; for (int q = 0; q < p; ++q) n += pieces_at(q); return n; }
-static_assert(piece_first(F1PS) == PPW1 && BARRIER_AT >= F1RING, "all pieces placed, behind fragments whose successors' ring slots the prologue fills");
-// vmcnt budget of the wait in front of fragment p of a slab (steady state)
-struct Fat1Sched {
-    int allowed[F1PS];
-};
-constexpr Fat1Sched make_fat1_sched() {
-    Fat1Sched s{};
-    int issued[4][F1PS] = {};
-    int seq = 0;
-    for (int p = 0; p < F1RING; ++p) issued[0][p] = seq++;
-    for (int k = 0; k < 3; ++k)
-        for (int p = 0; p < F1PS; ++p) {
-            if (k == 1) s.allowed[p] = seq - 1 - issued[k][p];
-            const int q = p + F1RING;
-            if (q >= F1PS) issued[k + 1][q - F1PS] = seq++;
-            else issued[k][q] = seq++;
-            seq += pieces_at(p);  // the next slab's pieces
-        }
-    return s;
-}
-struct Fat1SchedOf {
-    static constexpr Fat1Sched value = make_fat1_sched();
-};
+using Fat1 = Fat1x1<16>;   // the tile, the wait table and the slab body (fat1x1_dev.h): 256 pixel rows, 2 x 64 KB of LDS, 16 DMA pieces per wave and slab
+static_assert(Fat1::piece_first(F1PS) == Fat1::PPW && F1BARRIER_AT >= F1RING, "all pieces placed, behind fragments whose successors' ring slots the prologue fills");
+constexpr int F1ABL = ((FAT1_ABL & 1) ? F1_NO_WLOAD : 0) | ((FAT1_ABL & 2) ? F1_NO_DMA : 0) | ((FAT1_ABL & 4) ? F1_NO_LDSREAD : 0);
 
 __global__ __launch_bounds__(256) void conv1x1_fat_kernel(const Fat1Params p) {
-    using SCHED = Fat1SchedOf;
-    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * SLAB1];
+    __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * Fat1::SLAB];
     lds_u8_t* const smem = (lds_u8_t*)smem_;
     const unsigned lds0 = (unsigned)(size_t)smem;
 
@@ -110,25 +75,18 @@ __global__ __launch_bounds__(256) void conv1x1_fat_kernel(const Fat1Params p) {
 
     // tile = (pixel tile mt, channel tile nt): neighbouring workgroups (same XCD: blockIdx % 8) share the pixel tile
     const int nNt = p.Cout >> 8;
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, within = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-    }
+    const int bid = fat_xcd_tile(blockIdx.x, gridDim.x);
     const int mt = bid / nNt, nt = bid - mt * nNt;
     const int m0 = mt << 8;
 
-    // ---- pixel staging: piece i of this wave = rows 64 wave' ... of one 64-channel half: i = 2 j + h -> rows (wave + 4 j) * 8 .. + 7
-    // of half h; lane (lrow = lane >> 3, lchk = lane & 7) fetches chunk lchk ^ swizzle(row) of its row (igemm_kernel's layout:
-    // 16-byte chunk c of row r at c ^ ((r >> 1) & 7))
-    unsigned roff1[8], roff2[8];  // byte offset of the lane's row in x / x2 (+ its swizzled chunk)
+    // ---- pixel staging (Fat1x1::stage): byte offset of the lane's row in x / x2 (+ its swizzled chunk)
+    unsigned roff1[8], roff2[8];
     const int lrow = lane >> 3, lchk = lane & 7;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int row = (wave + 4 * j) * 8 + lrow;
         const int gm = min(m0 + row, p.M - 1);
-        const unsigned sw = (unsigned)((lchk ^ ((row >> 1) & 7)) << 4);
+        const unsigned sw = Fat1::swz(row, lchk);
         roff1[j] = (unsigned)gm * (unsigned)p.K1 * 2u + sw;
         roff2[j] = (unsigned)gm * (unsigned)p.K2 * 2u + sw;
     }
@@ -138,19 +96,13 @@ __global__ __launch_bounds__(256) void conv1x1_fat_kernel(const Fat1Params p) {
         const bool second = slab >= nslab1;  // uniform
         const unsigned char* src = second ? p.x2 + roff2[J] + (size_t)((slab - nslab1) * 256 + H * 128)
                                           : p.x + roff1[J] + (size_t)(slab * 256 + H * 128);
-        fat_dma(src, __builtin_amdgcn_readfirstlane(lds0 + buf * SLAB1 + H * HALF_BYTES + (wave + 4 * J) * 1024));
+        Fat1::stage<I>(src, lds0, buf, wave);
     };
-
-    // ---- pixel fragment b (rows 16 b + (lane & 15)) of k-step kk: half kk >> 1, chunk 4 (kk & 1) + (lane >> 4)
-    const int xbase = frow * 128 + ((fchunk ^ ((frow >> 1) & 7)) << 4);
+    const int xbase = Fat1::xbase(frow, fchunk);
 
     // ---- weight stream of this wave: fragment q of slab s at wpk + ((nt * 4 + wave) * nslab * F1PS + s * F1PS + q) KiB
     const unsigned char* wstream = p.wpk + (size_t)(nt * 4 + wave) * nslab * (F1PS * 1024);
     u32x4_t wr[F1RING];
-    auto issue_w = [&](auto slot_c, const unsigned char* slab_base, auto pos_c) {
-        constexpr int SLOT = decltype(slot_c)::value, POS = decltype(pos_c)::value;
-        fat_gload<(POS & 3) * 1024>(wr[SLOT], lane16, slab_base + (POS & ~3) * 1024);
-    };
 
     asm volatile("" ::: "a255");
     sfor<64>([&](auto qc) { fat_zero<decltype(qc)::value>(); });
@@ -158,68 +110,30 @@ __global__ __launch_bounds__(256) void conv1x1_fat_kernel(const Fat1Params p) {
     // ---- prologue: slab 0's pixel rows; then the first ring of weight fragments with slab 1's pieces behind fragments 4 .. 7 --
     // the order the loop issues them in behind fragments 12 .. 15 of the slab before, so that its counted waits hold from slab 0 on
     using std::integral_constant;
-    sfor<PPW1>([&](auto ic) { stage_piece(0, 0, ic); });
+    sfor<Fat1::PPW>([&](auto ic) { stage_piece(0, 0, ic); });
     sfor<F1RING>([&](auto ic) {
         constexpr int I = decltype(ic)::value;
-        issue_w(ic, wstream, ic);
-        sfor<pieces_at(I + F1RING)>([&](auto jc) {
-            stage_piece(nslab > 1 ? 1 : 0, 1, integral_constant<int, piece_first(I + F1RING) + decltype(jc)::value>{});
+        Fat1::issue_w<I>(wr[I], lane16, wstream);
+        sfor<Fat1::pieces_at(I + F1RING)>([&](auto jc) {
+            stage_piece(nslab > 1 ? 1 : 0, 1, integral_constant<int, Fat1::piece_first(I + F1RING) + decltype(jc)::value>{});
         });
     });
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1RING + PPW1) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1RING + Fat1::PPW) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
     u32x4_t xf[16];
-    auto ldx = [&](const lds_u8_t* sp, auto ks_c, auto b_c) {
-        constexpr int KS = decltype(ks_c)::value, B = decltype(b_c)::value;
-        const lds_u8_t* a = sp + (xbase ^ ((KS & 1) * 64));
-        return *reinterpret_cast<const lds_u32x4_t*>(a + (KS >> 1) * HALF_BYTES + B * 2048);
-    };
-    sfor<16>([&](auto bc) { xf[decltype(bc)::value] = ldx(smem, integral_constant<int, 0>{}, bc); });
+    sfor<16>([&](auto bc) { xf[decltype(bc)::value] = Fat1::ldx<0, decltype(bc)::value>(smem, xbase); });
     for (int slab = 0; slab < nslab; ++slab) {
         const bool more = slab + 1 < nslab;
         const unsigned char* ws = wstream + (size_t)slab * (F1PS * 1024);
         const unsigned char* wsn = wstream + (size_t)(more ? slab + 1 : 0) * (F1PS * 1024);  // past the end: slab 0 again (never used)
         const int ahead = slab + 2 < nslab ? slab + 2 : slab;  // (last two slabs: their own rows again, into the freed buffer)
-        const lds_u8_t* sp = smem + (slab & 1) * SLAB1;
-        const lds_u8_t* spn = smem + ((slab + 1) & 1) * SLAB1;
-
-        sfor<F1PS>([&](auto pc) {
-            constexpr int P = decltype(pc)::value;
-            constexpr int KS = P >> 2, A = P & 3, SL = P % F1RING;
-            fat_wait<SCHED::value.allowed[P]>(wr[SL]);
-            if constexpr (P == BARRIER_AT) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-            }
-            sfor<16>([&](auto bc) {
-                constexpr int B = decltype(bc)::value;
-                fat_mfma<A * 16 + B>(wr[SL], xf[B]);
-                if constexpr (A == 3 && !(FAT1_ABL & 4)) {  // the next k-step's fragment replaces this one right behind its last reader
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (KS + 1 < 4) xf[B] = ldx(sp, integral_constant<int, KS + 1>{}, bc);
-                    else xf[B] = ldx(spn, integral_constant<int, 0>{}, bc);
-                }
-            });
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int Q = P + F1RING;
-            if constexpr (!(FAT1_ABL & 1)) {
-            if constexpr (Q >= F1PS) issue_w(integral_constant<int, SL>{}, wsn, integral_constant<int, Q - F1PS>{});
-            else issue_w(integral_constant<int, SL>{}, ws, integral_constant<int, Q>{});
-            }
-            if constexpr (!(FAT1_ABL & 2))
-            sfor<pieces_at(P)>([&](auto ic) { stage_piece(ahead, slab & 1, integral_constant<int, piece_first(P) + decltype(ic)::value>{}); });
-        });
+        const lds_u8_t* sp = smem + (slab & 1) * Fat1::SLAB;
+        const lds_u8_t* spn = smem + ((slab + 1) & 1) * Fat1::SLAB;
+        Fat1::slab<F1ABL>(wr, xf, sp, spn, xbase, ws, wsn, lane16, [&](auto ic) { stage_piece(ahead, slab & 1, ic); });
     }
-    // fragments requested past the end are still landing
-#pragma unroll
-    for (int i = 0; i < F1RING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < F1RING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    fat_ring_drain(wr);
 
     // ---- epilogue: + bias, ReLU, round once; lane (f, row) holds channels 64 wave + 32 j + 8 f .. + 7 of (b, j): 16-byte stores
     const int cb = nt * 256 + wave * 64 + 8 * fchunk;
@@ -229,16 +143,11 @@ __global__ __launch_bounds__(256) void conv1x1_fat_kernel(const Fat1Params p) {
         const float4 b1 = *reinterpret_cast<const float4*>(p.bias + cb + 32 * j + 4);
         sfor<16>([&](auto bc) {
             constexpr int B = decltype(bc)::value;
-            const f32x4_t lo = fat_read<(2 * j) * 16 + B>(), hi = fat_read<(2 * j + 1) * 16 + B>();
-            float v[8] = {lo[0] + b0.x, lo[1] + b0.y, lo[2] + b0.z, lo[3] + b0.w, hi[0] + b1.x, hi[1] + b1.y, hi[2] + b1.z, hi[3] + b1.w};
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-            }
+            float v[8];
+            fat_bias8<(2 * j) * 16 + B, (2 * j + 1) * 16 + B>(v, 1.f, b0, b1);
+            fat_relu8(v, p.relu);
             const int gm = m0 + B * 16 + frow;
-            if (gm < p.M)
-                *reinterpret_cast<uint4*>(p.out + ((size_t)gm * p.Cout + cb + 32 * j) * 2) =
-                    make_uint4(pack_lp16x2(v[0], v[1]), pack_lp16x2(v[2], v[3]), pack_lp16x2(v[4], v[5]), pack_lp16x2(v[6], v[7]));
+            if (gm < p.M) fat_store8(p.out + ((size_t)gm * p.Cout + cb + 32 * j) * 2, v);
         });
     });
 }

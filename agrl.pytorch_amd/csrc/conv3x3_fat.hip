@@ -44,21 +44,6 @@ struct FatParams {
     int planes;                 // 1: write the fp32 result as fp16 planes [hi | (v - hi) 2^11 | hi] (agrl_conv3x3_packed_split16)
 };
 
-// fp32 -> the split-fp16 planes of round 6's conforming mode: hi = fp16(v) (round to nearest), lo = fp16((v - hi) 2^11) -- the difference is
-// exact in fp32, the scale keeps lo a NORMAL fp16 wherever hi is one (the consumer's weight segment for the lo plane carries the 2^-11)
-__device__ __forceinline__ void split16_pack8(const float v[8], uint4& hi, uint4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h[e] = pack_lp16x2(v[2 * e], v[2 * e + 1]);
-        float a, b;
-        unpack_lp16x2(h[e], a, b);
-        l[e] = pack_lp16x2((v[2 * e] - a) * 2048.f, (v[2 * e + 1] - b) * 2048.f);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 #ifndef FAT_ABL
 #define FAT_ABL 0  // timing ablations (results wrong): 1 no weight loads in the loop, 2 no patch DMA, 4 no LDS reads, 8 no MFMA; 16: phase stamps (s_memtime, results right; agrl_fat3_trace_buffer, tools/fat3_timeline.py)
 #endif
@@ -69,31 +54,9 @@ constexpr int FRING = FAT_RING;  // weight fragments in flight per wave
 constexpr int FPS = 9 * 2 * 4;  // weight fragments per slab and wave: 9 taps x 2 k-steps x 4 channel fragments
 constexpr int PATCH_PIECES = 23, PATCH_BYTES_F = PATCH_PIECES * 1024;  // 18 x 10 halo pixels x 128 B, rounded to whole DMA pieces
 
-// vmcnt budget of the wait in front of fragment p of a slab (steady state): operations issued after that fragment's load
-template <int PPW>  // patch DMA pieces per wave and slab, one behind the first fragment of k-steps 0 .. PPW - 1
-struct FatSched {
-    int allowed[FPS];
-};
+// counted waits (fat_dev.h): one patch DMA piece behind the first weight fragment of k-steps 0 .. PPW - 1 (PPW pieces per wave and slab)
 template <int PPW>
-constexpr FatSched<PPW> make_fat_sched() {
-    FatSched<PPW> s{};
-    int issued[4][FPS] = {};
-    int seq = 0;
-    for (int p = 0; p < FRING; ++p) issued[0][p] = seq++;
-    for (int k = 0; k < 3; ++k)
-        for (int p = 0; p < FPS; ++p) {
-            if (k == 1) s.allowed[p] = seq - 1 - issued[k][p];
-            const int q = p + FRING;
-            if (q >= FPS) issued[k + 1][q - FPS] = seq++;
-            else issued[k][q] = seq++;
-            if ((p & 3) == 0 && (p >> 2) < PPW) seq += 1;  // the next slab's patch piece
-        }
-    return s;
-}
-template <int PPW>
-struct FatSchedOf {
-    static constexpr FatSched<PPW> value = make_fat_sched<PPW>();
-};
+constexpr auto FAT_SCHED = fat_ring_sched<FRING, FPS>([](int p) { return (p & 3) == 0 && (p >> 2) < PPW; });
 
 #if FAT_ABL & 16
 __device__ unsigned long long* g_fat3_trace = nullptr;   // profiling build: 16 stamps per workgroup
@@ -111,7 +74,6 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
     constexpr int NBF = 8 * PB;                                   // pixel (B) fragments per wave
     constexpr int SLAB = PB * PATCH_BYTES_F;                      // one slab's patches
     constexpr int PPW = (PB * PATCH_PIECES + 3) / 4;              // patch pieces per wave and slab (the last ones may be dummies)
-    using SCHED = FatSchedOf<PPW>;
     static_assert(PPW <= 18, "one patch piece per k-step");
     static_assert(FPS % FRING == 0, "a slab is a whole number of ring turns");
     __shared__ __attribute__((aligned(16))) unsigned char smem_[2 * SLAB + 1024];
@@ -126,12 +88,7 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
 
     // tile = (pixel tile mt, channel tile nt): neighbouring workgroups (same XCD: blockIdx % 8) share the pixel tile
     const int nNt = p.Cout >> 8;
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, within = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-    }
+    const int bid = fat_xcd_tile(blockIdx.x, gridDim.x);
     const int mt = bid / nNt, nt = bid - mt * nNt;
     const int tw = p.W >> 3, th = p.H >> 4;
     auto block_origin = [&](int bsel, int& img, int& oy0, int& ox0) {
@@ -220,7 +177,7 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
         sfor<FPS>([&](auto pc) {
             constexpr int P = decltype(pc)::value;
             constexpr int KS = P >> 2, A = P & 3, SL = P % FRING;
-            fat_wait<SCHED::value.allowed[P]>(wr[SL]);
+            fat_wait<FAT_SCHED<PPW>.allowed[P]>(wr[SL]);
             sfor<NBF>([&](auto bc) {
                 constexpr int B = decltype(bc)::value;
                 if constexpr (!(FAT_ABL & 8)) fat_mfma<A * NBF + B>(wr[SL], xf[B]);
@@ -238,13 +195,7 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
         });
     }
     FAT3_STAMP(11);
-    // fragments requested past the end are still landing
-#pragma unroll
-    for (int i = 0; i < FRING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < FRING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    fat_ring_drain(wr);
     FAT3_STAMP(12);
 
     // ---- epilogue: + bias, ReLU, round once; lane (f, pixel) holds channels 64 wave + 32 j + 8 f .. + 7 of (b, j): 16-byte stores
@@ -256,30 +207,16 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
         const float4 b1 = *reinterpret_cast<const float4*>(p.bias + cb + 32 * j + 4);
         sfor<NBF>([&](auto bc) {
             constexpr int B = decltype(bc)::value;
-            const f32x4_t lo = fat_read<(2 * j) * NBF + B>(), hi = fat_read<(2 * j + 1) * NBF + B>();
-            // (alpha = 1: fmaf(1, acc, b) == acc + b, the round-5 results bit for bit)
-            float v[8] = {fmaf(alpha, lo[0], b0.x), fmaf(alpha, lo[1], b0.y), fmaf(alpha, lo[2], b0.z), fmaf(alpha, lo[3], b0.w),
-                          fmaf(alpha, hi[0], b1.x), fmaf(alpha, hi[1], b1.y), fmaf(alpha, hi[2], b1.z), fmaf(alpha, hi[3], b1.w)};
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-            }
+            float v[8];
+            fat_bias8<(2 * j) * NBF + B, (2 * j + 1) * NBF + B>(v, alpha, b0, b1);   // (alpha = 1: the round-5 results bit for bit)
+            fat_relu8(v, p.relu);
             if (PB * mt + (B >> 3) < p.nblocks) {
                 int img, oy0, ox0;
                 block_origin(B >> 3, img, oy0, ox0);
                 const int m = (B & 7) * 16 + fp;
                 const size_t gm = ((size_t)img * p.H + oy0 + (m >> 3)) * p.W + ox0 + (m & 7);
-                if (p.planes) {
-                    uint4 ph, pl;
-                    split16_pack8(v, ph, pl);
-                    unsigned char* o = p.out + (gm * 3 * p.Cout + cb + 32 * j) * 2;
-                    *reinterpret_cast<uint4*>(o) = ph;
-                    *reinterpret_cast<uint4*>(o + (size_t)p.Cout * 2) = pl;
-                    *reinterpret_cast<uint4*>(o + (size_t)p.Cout * 4) = ph;
-                } else {
-                    *reinterpret_cast<uint4*>(p.out + (gm * p.Cout + cb + 32 * j) * 2) =
-                        make_uint4(pack_lp16x2(v[0], v[1]), pack_lp16x2(v[2], v[3]), pack_lp16x2(v[4], v[5]), pack_lp16x2(v[6], v[7]));
-                }
+                if (p.planes) fat_store8_split16(p.out + (gm * 3 * p.Cout + cb + 32 * j) * 2, (size_t)p.Cout * 2, v);
+                else fat_store8(p.out + (gm * p.Cout + cb + 32 * j) * 2, v);
             }
         });
     });
@@ -304,30 +241,9 @@ __global__ __launch_bounds__(256) void conv3x3_fat_kernel(const FatParams p) {
 constexpr int HRING = 12;                // weight fragments in flight per wave (a slab = 36 = 3 ring turns)
 constexpr int HPS = 9 * 2 * 2;           // weight fragments per slab and wave: 9 taps x 2 k-steps x 2 channel fragments
 constexpr int HPPW = (PATCH_PIECES + 3) / 4;
-struct HalfSched {
-    int allowed[HPS];
-};
-constexpr HalfSched make_half_sched() {
-    HalfSched s{};
-    int issued[4][HPS] = {};
-    int seq = 0;
-    for (int p = 0; p < HRING; ++p) issued[0][p] = seq++;
-    for (int k = 0; k < 3; ++k)
-        for (int p = 0; p < HPS; ++p) {
-            if (k == 1) s.allowed[p] = seq - 1 - issued[k][p];
-            const int q = p + HRING;
-            if (q >= HPS) issued[k + 1][q - HPS] = seq++;
-            else issued[k][q] = seq++;
-            if ((p & 1) == 0 && (p >> 1) < HPPW) seq += 1;  // the next slab's patch piece
-        }
-    return s;
-}
-struct HalfSchedOf {
-    static constexpr HalfSched value = make_half_sched();
-};
+constexpr auto HALF_SCHED = fat_ring_sched<HRING, HPS>([](int p) { return (p & 1) == 0 && (p >> 1) < HPPW; });   // one patch piece behind the first fragment of k-steps 0 .. HPPW - 1
 
 __global__ __launch_bounds__(256, 2) void conv3x3_half_kernel(const FatParams p, int stagger, int first, int halves) {
-    using SCHED = HalfSchedOf;
     using std::integral_constant;
     constexpr int NBF = 8;
     constexpr int SLAB = PATCH_BYTES_F;
@@ -353,12 +269,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_half_kernel(const FatParams p,
     const int nNt = halves == 1 ? 1 : p.Cout >> 8;
     const int per_half = halves == 1 ? (int)gridDim.x : (int)(gridDim.x >> 1);
     const int half = (int)blockIdx.x >= per_half ? 1 : 0;
-    int bid = (int)blockIdx.x - half * per_half;
-    {
-        const int nblk = per_half, q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, within = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-    }
+    const int bid = fat_xcd_tile((int)blockIdx.x - half * per_half, per_half);
     const int mt = bid / nNt, nt = bid - mt * nNt;
     const int tw = p.W >> 3, th = p.H >> 4;
     const int img = mt / (tw * th);
@@ -429,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_half_kernel(const FatParams p,
         sfor<HPS>([&](auto pc) {
             constexpr int P = decltype(pc)::value;
             constexpr int KS = P >> 1, A = P & 1, SL = P % HRING;
-            fat_wait<SCHED::value.allowed[P]>(wr[SL]);
+            fat_wait<HALF_SCHED.allowed[P]>(wr[SL]);
             sfor<NBF>([&](auto bc) {
                 constexpr int B = decltype(bc)::value;
                 fat_mfma<A * NBF + B>(wr[SL], xf[B]);
@@ -445,12 +356,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_half_kernel(const FatParams p,
             if constexpr (A == 0 && KS < HPPW) stage_patch_piece(more ? slab + 1 : slab, (slab + 1) & 1, KS);
         });
     }
-#pragma unroll
-    for (int i = 0; i < HRING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < HRING; ++i) asm volatile("" : "+v"(wr[i]));
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    fat_ring_drain(wr);
 
     // ---- epilogue: + bias, ReLU, round once; lane (f, pixel) holds channels 64 grp + 32 (wave & 1) + 8 f .. + 7 of pixel fragment b
     const int cb = nt * 256 + grp * 64 + 32 * (wave & 1) + 8 * fchunk;
@@ -459,26 +365,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_half_kernel(const FatParams p,
     const float alpha = p.alpha;
     sfor<NBF>([&](auto bc) {
         constexpr int B = decltype(bc)::value;
-        const f32x4_t lo = fat_read<B>(), hi = fat_read<NBF + B>();
-        float v[8] = {fmaf(alpha, lo[0], b0.x), fmaf(alpha, lo[1], b0.y), fmaf(alpha, lo[2], b0.z), fmaf(alpha, lo[3], b0.w),
-                      fmaf(alpha, hi[0], b1.x), fmaf(alpha, hi[1], b1.y), fmaf(alpha, hi[2], b1.z), fmaf(alpha, hi[3], b1.w)};
-        if (p.relu) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = relu_nan(v[e]);
-        }
+        float v[8];
+        fat_bias8<B, NBF + B>(v, alpha, b0, b1);
+        fat_relu8(v, p.relu);
         const int m = B * 16 + fp;
         const size_t gm = ((size_t)img * p.H + oy0 + (m >> 3)) * p.W + ox0 + (m & 7);
-        if (p.planes) {
-            uint4 ph, pl;
-            split16_pack8(v, ph, pl);
-            unsigned char* o = p.out + (gm * 3 * p.Cout + cb) * 2;
-            *reinterpret_cast<uint4*>(o) = ph;
-            *reinterpret_cast<uint4*>(o + (size_t)p.Cout * 2) = pl;
-            *reinterpret_cast<uint4*>(o + (size_t)p.Cout * 4) = ph;
-        } else {
-            *reinterpret_cast<uint4*>(p.out + (gm * p.Cout + cb) * 2) =
-                make_uint4(pack_lp16x2(v[0], v[1]), pack_lp16x2(v[2], v[3]), pack_lp16x2(v[4], v[5]), pack_lp16x2(v[6], v[7]));
-        }
+        if (p.planes) fat_store8_split16(p.out + (gm * 3 * p.Cout + cb) * 2, (size_t)p.Cout * 2, v);
+        else fat_store8(p.out + (gm * p.Cout + cb) * 2, v);
     });
 }
 

@@ -51,13 +51,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const IgemmParams p, 
     const int lrow = lane >> 3, lchk = lane & 7;
 
     const int nNt = (p.N + BN - 1) / BN;
-    const int nblk = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, within = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-    }
+    const int bid = fat_xcd_tile(blockIdx.x, gridDim.x);
     const int mt = bid / nNt;
     const int nt = bid - mt * nNt;
     const int n0 = nt * BN;

@@ -149,6 +149,14 @@ struct Frag<f32h_t> {
 
 __device__ inline int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
+// Workgroup bid of nblk -> tile index: the workgroups of one XCD (bid % 8) take a contiguous range of tiles, in launch order, so that
+// the channel tiles of one pixel tile (neighbouring indices) share that XCD's L2. (igemm_wide.hip has its own map with an N-major form.)
+__device__ __forceinline__ int fat_xcd_tile(int bid, int nblk) {
+    const int q = nblk >> 3, r = nblk & 7;
+    const int xcd = bid & 7, within = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
+}
+
 template <typename TOUT>
 __device__ inline void store4(TOUT* p, const float v[4]);
 template <>

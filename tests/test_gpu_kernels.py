@@ -498,6 +498,25 @@ def test_conv3x3_packed(case, monkeypatch):
         ops.call("agrl_conv3x3_packed_bn_act", ops.ptr(dx), ops.ptr(packed), ops.ptr(b.to(DEV)), ops.ptr(out), N, 10, 6, Cin, Cout, 1, None)
 
 
+def assert_rejects_each(name, good, bad):
+    """``good`` is an argument list that entry point ``name`` accepts: the smallest shape of the 1x1 family (M = 128, K = 128, Cout = 256)
+    on zeroed allocations with room for every size changed below, so that even a wrongly accepted call stays inside them. Each
+    (index, value) of ``bad`` replaces ONE argument and must be refused."""
+    from torchreid import hip_ops as ops
+    ops.call(name, *good)
+    for i, v in bad:
+        with pytest.raises(_hip.HipKernelError):
+            ops.call(name, *(good[:i] + [v] + good[i + 1:]))
+    torch.cuda.synchronize()
+
+
+def small_1x1_buffers():
+    """x / x2 / residual / out / packed weights (16-bit) and bias / pooled sums (fp32) of the smallest accepted 1x1 shape, 1 MiB each"""
+    lp = [torch.zeros(1 << 19, dtype=LP_DTYPE, device=DEV) for _ in range(5)]
+    f32 = [torch.zeros(1 << 18, device=DEV) for _ in range(2)]
+    return lp, f32
+
+
 @pytest.mark.parametrize("case", [(1, 16, 8, 128, 0, 256, True), (3, 10, 6, 256, 0, 512, False), (40, 16, 8, 2048, 0, 512, True),
                                   (37, 16, 8, 1024, 512, 2048, True), (2, 16, 8, 256, 128, 256, True), (250, 16, 8, 1024, 0, 512, True)])
 def test_conv1x1_packed(case):
@@ -547,6 +566,12 @@ def test_conv1x1_packed(case):
         assert torch.equal(ops.conv1x1_packed_res(dx, packed, b.to(DEV), Cout, None, relu), out)
     with pytest.raises(_hip.HipKernelError):
         ops.call("agrl_conv1x1_packed_bn_act", ops.ptr(dx), None, ops.ptr(packed), ops.ptr(b.to(DEV)), ops.ptr(out), N * H * W, K1 + 64, 0, Cout, 1, None)
+    # a pointer that is not 16-byte aligned, K not a multiple of 128, Cout not a multiple of 256
+    (sx, sx2, _, so, spk), (sb, _) = small_1x1_buffers()
+    assert_rejects_each("agrl_conv1x1_packed_bn_act", [ops.ptr(sx), None, ops.ptr(spk), ops.ptr(sb), ops.ptr(so), 128, 128, 0, 256, 1, None],
+                        [(0, sx.data_ptr() + 2), (6, 192), (8, 384)])
+    assert_rejects_each("agrl_conv1x1_packed_dual_duo", [ops.ptr(sx), ops.ptr(sx2), ops.ptr(spk), ops.ptr(sb), ops.ptr(so), 128, 128, 128, 256, 1, None],
+                        [(1, sx2.data_ptr() + 2), (6, 192), (7, 192), (8, 384)])
 
 
 STRIDED_DUAL_CASES = [(8, 64, 32, 256, 128, 512, 2), (8, 32, 16, 512, 256, 1024, 2), (3, 7, 5, 128, 128, 256, 2), (2, 9, 6, 128, 256, 256, 3),
@@ -595,6 +620,10 @@ def test_conv1x1_packed_dual_strided(case):
     with pytest.raises(_hip.HipKernelError):
         ops.call("agrl_conv1x1_packed_dual_strided", ops.ptr(dx), ops.ptr(dy), ops.ptr(packed), ops.ptr(bias), ops.ptr(out), N, Hi, Wi, s,
                  K1 + 64, K2, Cout, 1, None)
+    (sx, sx2, _, so, spk), (sb, _) = small_1x1_buffers()   # misaligned pointer, K1 / K2 not multiples of 128, Cout not a multiple of 256
+    assert_rejects_each("agrl_conv1x1_packed_dual_strided",
+                        [ops.ptr(sx), ops.ptr(sx2), ops.ptr(spk), ops.ptr(sb), ops.ptr(so), 1, 16, 8, 1, 128, 128, 256, 1, None],
+                        [(4, so.data_ptr() + 2), (9, 192), (10, 192), (11, 384)])
 
 
 DUO_CASES = [(256, 16, 8, 512, 2048, True, True), (1, 16, 8, 512, 2048, True, True), (3, 10, 6, 128, 256, True, False),
@@ -636,9 +665,13 @@ def test_conv1x1_packed_res(case):
     check_conv(out, x, w, b, res=res, relu=relu, name="conv1x1 duo %s" % (case,))
     with pytest.raises(_hip.HipKernelError):
         ops.call("agrl_conv1x1_packed_res_bn_act", ops.ptr(dx), ops.ptr(packed), ops.ptr(b.to(DEV)), None, ops.ptr(out), N * H * W, K + 64, Cout, 1, None)
+    (sx, _, sres, so, spk), (sb, _) = small_1x1_buffers()   # misaligned pointer, K not a multiple of 128, Cout not a multiple of 256
+    assert_rejects_each("agrl_conv1x1_packed_res_bn_act", [ops.ptr(sx), ops.ptr(spk), ops.ptr(sb), ops.ptr(sres), ops.ptr(so), 128, 128, 256, 1, None],
+                        [(3, sres.data_ptr() + 2), (6, 192), (7, 384)])
 
 
-@pytest.mark.parametrize("case", ["res", "plain_k2048", "plain_k1024", "dual", "strided_l2", "strided_l3", "pool_parts", "pool_sum", "ragged", "two_slabs"])
+@pytest.mark.parametrize("case", ["res", "plain_k2048", "plain_k1024", "dual", "strided_l2", "strided_l3", "pool_parts", "pool_sum", "ragged", "two_slabs",
+                                  "one_channel_tile"])
 def test_conv1x1_duo_persistent_form_is_bit_identical(case, monkeypatch):
     """The default dispatch since round 6 (conv1x1_duo_persist_kernel; AGRL_DUO_PERSIST=0 is the one-shot form it is compared with) -- two persistent workgroups per CU, the next tile's first slab and weight
     ring requested during the current tile's last slabs, the epilogue in two 64-row passes inside ONE pixel buffer) against the one-shot
@@ -680,6 +713,10 @@ def test_conv1x1_duo_persistent_form_is_bit_identical(case, monkeypatch):
             x, w, b, r = rnd((300, 16, 8, 256), relu=True), rnd((1024, 256), 0.06), rnd((1024,)).float(), rnd((300, 16, 8, 1024))
             pk = ops.conv1x1_pack(w)
             return [ops.conv1x1_packed_res(x, pk, b, 1024, r, True)]
+        if case == "one_channel_tile":   # Cout = 256 and 520 pixel tiles: where the persistent form's tile map and the one-shot form's differ most
+            x, w, b, r = rnd((520, 16, 8, 256), relu=True), rnd((256, 256), 0.06), rnd((256,)).float(), rnd((520, 16, 8, 256))
+            pk = ops.conv1x1_pack(w)
+            return [ops.conv1x1_packed_res(x, pk, b, 256, r, True)]
         # ragged: 131 frames x 100 px (M = 13100: a partial last tile), K = 384 (three slabs: odd), Cout = 1280 (five channel tiles)
         x, w, b, r = rnd((131, 10, 10, 384), relu=True), rnd((1280, 384), 0.05), rnd((1280,)).float(), rnd((131, 10, 10, 1280))
         pk = ops.conv1x1_pack(w)
@@ -743,6 +780,15 @@ def test_conv1x1_packed_res_pool(cfg):
         arr3 = (C.c_int * 1)(3)
         ops.call("agrl_conv1x1_packed_res_pool", ops.ptr(x), ops.ptr(packed), ops.ptr(b), ops.ptr(res), ops.ptr(pooled), None,
                  N, 16, 8, Cin, Cout, 1, arr3, 1, 1, None)
+    # misaligned pointer, K not a multiple of 128, Cout not a multiple of 256, bins that are not whole quarters, 17 bins
+    (sx, _, sres, _, spk), (sb, spool) = small_1x1_buffers()
+    one, ones17 = (C.c_int * 1)(1), (C.c_int * 17)(*([1] * 17))
+    assert_rejects_each("agrl_conv1x1_packed_res_pool",
+                        [ops.ptr(sx), ops.ptr(spk), ops.ptr(sb), ops.ptr(sres), ops.ptr(spool), None, 1, 16, 8, 128, 256, 1, one, 1, 1, None],
+                        [(4, spool.data_ptr() + 2), (9, 192), (10, 384), (12, arr3)])
+    with pytest.raises(_hip.HipKernelError):   # 17 bins
+        ops.call("agrl_conv1x1_packed_res_pool", ops.ptr(sx), ops.ptr(spk), ops.ptr(sb), ops.ptr(sres), ops.ptr(spool), None,
+                 1, 16, 8, 128, 256, 1, ones17, 17, 1, None)
 
 
 STRESS_KINDS = ["bnfold", "bias", "residual", "straddle", "tiny"]
@@ -1598,6 +1644,12 @@ def test_split16_entry_points_validate_their_arguments():
         ops.call("agrl_conv1x1_split16", ops.ptr(x3), ops.ptr(pk), ops.ptr(b), None, ops.ptr(out), 512, 320, 256, 1, 1.0, 0, None)
     with pytest.raises(_hip.HipKernelError):   # layout bits beyond 3
         ops.call("agrl_conv1x1_split16", ops.ptr(x3), ops.ptr(pk), ops.ptr(b), None, ops.ptr(out), 512, 384, 256, 1, 1.0, 4, None)
+    import ctypes as C
+    pooled = torch.zeros((4, 16, 256), device=DEV)   # bins that are not whole quarters, 17 bins, a pointer that is not 16-byte aligned
+    good = [ops.ptr(x3), ops.ptr(pk), ops.ptr(b), None, ops.ptr(pooled), 4, 16, 8, 384, 256, 1, (C.c_int * 1)(1), 1, 1, 1.0, 0, None]
+    assert_rejects_each("agrl_conv1x1_split16_pool", good, [(11, (C.c_int * 1)(3)), (4, pooled.data_ptr() + 2)])
+    with pytest.raises(_hip.HipKernelError):
+        ops.call("agrl_conv1x1_split16_pool", *(good[:11] + [(C.c_int * 17)(*([1] * 17)), 17] + good[13:]))
     with pytest.raises(_hip.HipKernelError):   # scale of the weight planes must be a power of two
         ops.to_split16_weight_planes(x.view(-1, 128), 3.0)
     with pytest.raises(_hip.HipKernelError):   # D3 must be a multiple of 3
