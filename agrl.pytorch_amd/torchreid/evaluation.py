@@ -20,6 +20,7 @@ import torch
 
 from torchreid import hip_ops as ops
 from torchreid import parallel
+from torchreid.device_transforms import eval_geometry
 from torchreid.metrics.distance import hip_distmat_device, hip_distmat_topk_device
 
 
@@ -39,7 +40,8 @@ def device_prefetch(batches, device):
     loop, train_vidreid_xent_htri.py:460, and its loaders hand over pinned tensors, :222-247 ``pin_memory``): with pinned
     sources the frames of a 256-frame batch -- 100 MB as fp32, 25 MB as the uint8 a decoder produces, which the models take as
     they are -- cross PCIe under the previous batch's forward. The dtype is kept. Yields the same tuples with imgs / adj on
-    ``device``; tensors already there pass through."""
+    ``device``; tensors already there pass through. A fifth element (the valid-extent array of a padded ragged batch,
+    ``extract_features(frame_size=...)``) is passed through untouched: it stays a host array."""
     if device.type != "cuda":
         for item in batches:
             yield item
@@ -48,12 +50,12 @@ def device_prefetch(batches, device):
     main = torch.cuda.current_stream(device)
 
     def upload(item):
-        imgs, pid, camid, adj = item
+        imgs, pid, camid, adj = item[:4]
         with torch.cuda.stream(copy_stream):
             imgs_d, adj_d = imgs.to(device, non_blocking=True), adj.to(device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(copy_stream)
-        return imgs_d, pid, camid, adj_d, done
+        return (imgs_d, pid, camid, adj_d) + tuple(item[4:]), done
 
     pending = None
     for item in batches:
@@ -66,20 +68,27 @@ def device_prefetch(batches, device):
 
 
 def _claim(pending, main):
-    imgs_d, pid, camid, adj_d, done = pending
+    item, done = pending
     main.wait_event(done)
-    imgs_d.record_stream(main)
-    adj_d.record_stream(main)
-    return imgs_d, pid, camid, adj_d
+    item[0].record_stream(main)
+    item[3].record_stream(main)
+    return item
 
 
 @torch.no_grad()
-def extract_features(model, batches, pool="avg", prefetch=True, local_only=False, sync_ranks=None):
+def extract_features(model, batches, pool="avg", prefetch=True, local_only=False, sync_ranks=None, frame_size=None):
     """``batches`` yields (imgs, pids, camids, adj) like the reference's loaders; imgs is (b,S,3,H,W) or, for the
     dense samplers, (b,n,S,3,H,W) with adj (b,n,V,V). Returns (features (N,D) on the model's device, pids, camids).
     imgs is fp32 (normalised by the loader's transform_test) or uint8 -- channel-first as above or channel-last, (b,S,H,W,3) /
     (b,n,S,H,W,3), straight from the decoder: a quarter of the PCIe bytes and no ToTensor / Normalize on the host; the model
     normalises inside its stem kernel (model.pixel_mean / pixel_std), bit-identical to the fp32 route.
+
+    ``frame_size=(H, W)``: the size the model takes. uint8 channel-last batches of any other spatial size -- frames as decoded -- are
+    resampled to it on the device before the model call (``hip_ops.clip_resample``: the reference's GroupResize, byte for byte
+    Pillow's BILINEAR resize). A batch item may then be a 5-tuple whose last element is the int array (b,[n,]S,2) of each frame's valid
+    (height, width) inside a padded container, for ragged batches; without it every frame fills its container. Batches already
+    (H, W) pass through; a uint8 channel-first batch or an fp32 batch of another size raises ValueError (neither can be resampled
+    here). The default ``None`` resamples nothing and takes 4-tuples only.
 
     Under an active process group (world > 1) the call is COLLECTIVE by default: every rank extracts its slice and then meets
     the others in ``match_and_rank``, so the non-finite flag is all-reduced (MAX) -- by every rank, whatever device its model
@@ -93,13 +102,21 @@ def extract_features(model, batches, pool="avg", prefetch=True, local_only=False
     nonfinite = None
     if prefetch:
         batches = device_prefetch(batches, device)
-    for imgs, pid, camid, adj in batches:
+    for item in batches:
+        if len(item) not in ((4,) if frame_size is None else (4, 5)):
+            raise ValueError("a batch is (imgs, pids, camids, adj)%s, got %d elements" % (
+                "; a fifth element, the frames' valid extents, needs frame_size" if frame_size is None else " or that plus the valid extents",
+                len(item)))
+        imgs, pid, camid, adj = item[:4]
+        sizes = item[4] if len(item) > 4 else None
         imgs, adj = imgs.to(device, non_blocking=True), adj.to(device, non_blocking=True)
         clips = 1
         if imgs.dim() == 6:
             b, clips = imgs.shape[:2]
             imgs = imgs.reshape((b * clips,) + tuple(imgs.shape[2:]))   # whichever layout the trailing axes have
             adj = adj.reshape((b * clips,) + tuple(adj.shape[2:]))
+        if frame_size is not None:
+            imgs = _to_frame_size(imgs, sizes, frame_size)
         raw = model(imgs, adj)
         if raw.is_cuda:   # accumulated on the device, read once after the last batch: no per-batch synchronisation
             bad = ~torch.isfinite(raw).all()
@@ -126,6 +143,31 @@ def extract_features(model, batches, pool="avg", prefetch=True, local_only=False
                     ": activations (or BatchNorm-folded weights) left fp16's range -- set AGRL_HIP_LP16=bf16 (libagrl_hip_bf16.so) or "
                     "hip_precision='fp32'" if _hip.LP_NAME == "fp16" and getattr(model, "hip_precision", "fp32") == "fp16" else ""))
     return out, np.asarray(pids), np.asarray(camids)
+
+
+def _to_frame_size(imgs, sizes, frame_size):
+    """(B,S,...) clips on the device -> clips of ``frame_size``: ones already that size pass (either layout, either dtype) unless valid
+    extents came with them; uint8 channel-last ones of another size, or with extents, are resampled; anything else is a ValueError."""
+    H, W = int(frame_size[0]), int(frame_size[1])
+    if imgs.dim() != 5:
+        raise ValueError("clips are (b,[n,]S,3,H,W) or (b,[n,]S,H,W,3), got %s" % (tuple(imgs.shape),))
+    layout = ops.frames_layout(imgs.shape)
+    fits = tuple(imgs.shape[3:]) == (H, W) if layout == 'nchw' else tuple(imgs.shape[2:4]) == (H, W)
+    if fits and sizes is None:
+        return imgs
+    if imgs.dtype != torch.uint8 or layout != 'nhwc':
+        raise ValueError("a %s channel-%s batch of %s cannot be resampled to frame_size=%s%s: hand over the decoded uint8 channel-last frames" % (
+            imgs.dtype, "first" if layout == 'nchw' else "last", tuple(imgs.shape[2:]), (H, W),
+            "" if sizes is None else " (valid extents were given)"))
+    B, S, Hs, Ws = imgs.shape[:4]
+    if sizes is None:
+        sizes = np.broadcast_to(np.array([Hs, Ws], dtype=np.int64), (B, S, 2))
+    else:
+        sizes = np.asarray(sizes.cpu() if isinstance(sizes, torch.Tensor) else sizes)
+        if sizes.size != B * S * 2:
+            raise ValueError("valid extents are (b,[n,]S,2) for clips of %s, got %s" % (tuple(imgs.shape[:2]), sizes.shape))
+    geometry = eval_geometry(sizes.reshape(B * S, 2))
+    return ops.clip_resample(imgs.contiguous().view(B * S, Hs, Ws, 3), geometry, (H, W)).view(B, S, H, W, 3)
 
 
 def _i32(a, device):

@@ -6,8 +6,10 @@ input's device, and launches on the calling thread's current HIP stream. No arit
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -153,6 +155,172 @@ def clips_to_float(x, mean=PIXEL_MEAN, std=PIXEL_STD):
     if x.is_cuda:
         return frames_normalize(x.reshape((B * S,) + tuple(x.shape[2:])), mean, std).view(B, S, 3, H, W)
     return frames_normalize_reference(x, mean, std)
+
+
+# ---- resize / crop / flip of uint8 clips (include/agrl_hip.h, "uint8 frames": agrl_clip_resample_u8) ------------------------
+RESAMPLE_TAPS = 17        # taps per output element the kernel holds: a downscale of up to RESAMPLE_MAX_SCALE per axis
+RESAMPLE_MAX_SCALE = 8
+RESAMPLE_MAX_OUT = 512
+_RESAMPLE_BITS = 22       # Pillow's PRECISION_BITS for 8-bit channels
+
+
+@functools.lru_cache(maxsize=4096)
+def _resample_taps(in_size, out_size, max_taps):
+    if in_size < 1 or out_size < 1:
+        raise ValueError("resample_taps: sizes are >= 1, got in=%d out=%d" % (in_size, out_size))
+    if in_size == out_size:   # Pillow skips the pass: the identity as one tap of weight 1
+        k = np.zeros((out_size, max_taps or 1), dtype=np.int32)
+        k[:, 0] = 1 << _RESAMPLE_BITS
+        bounds = np.stack([np.arange(out_size), np.ones(out_size, dtype=np.int64)], 1).astype(np.int32)
+    else:
+        scale = np.float64(in_size) / np.float64(out_size)
+        fs = np.float64(max(scale, 1.0))
+        support = fs          # the triangle filter's support of 1, stretched by the downscale
+        center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+        lo = np.maximum((center - support + 0.5).astype(np.int64), 0)          # astype truncates towards zero, as C's (int) does
+        hi = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+        count = hi - lo
+        if max_taps is not None:
+            count = np.minimum(count, max_taps)
+        width = max_taps or int(count.max())
+        j = lo[:, None] + np.arange(width, dtype=np.int64)[None, :]
+        t = np.abs((j.astype(np.float64) - center[:, None] + 0.5) / fs)
+        w = np.where((np.arange(width)[None, :] < count[:, None]) & (t < 1.0), 1.0 - t, 0.0)
+        total = np.zeros(out_size, dtype=np.float64)
+        for c in range(width):   # tap by tap, as the C loop accumulates (np.sum adds pairwise)
+            total = total + w[:, c]
+        k = (0.5 + (w / total[:, None]) * np.float64(1 << _RESAMPLE_BITS)).astype(np.int32)
+        bounds = np.stack([lo, count], 1).astype(np.int32)
+    k.setflags(write=False)
+    bounds.setflags(write=False)
+    return k, bounds
+
+
+def resample_taps(in_size, out_size, max_taps=None):
+    """The integer filter taps of Pillow's ``Image.resize(..., BILINEAR)`` along one axis of ``in_size`` -> ``out_size`` elements, all in
+    fp64 as ImagingResample computes them: scale = in / out, fs = max(scale, 1), center = (i + 0.5) scale, taps j in
+    [max(int(center - fs + 0.5), 0), min(int(center + fs + 0.5), in)) with w = 1 - |(j - center + 0.5) / fs| (0 from 1 on), divided by their
+    sum and stored as int(0.5 + w 2^22). ``in_size == out_size`` is the identity: one tap of 2^22 at j = i.
+    -> (k int32 (out, width) zero behind each row's taps, bounds int32 (out, 2) = (lo, count)); read-only, cached.
+    ``max_taps``: what agrl_resample_taps_u8 and the resample kernel hold (RESAMPLE_TAPS): width = max_taps, a row with more taps keeps
+    its first max_taps, normalised among themselves -- identical to the full row whenever in <= RESAMPLE_MAX_SCALE * out."""
+    return _resample_taps(int(in_size), int(out_size), None if max_taps is None else int(max_taps))
+
+
+def _resample_axis(a, out_size):
+    """One pass of the resample along axis 0 of an integer array: (2^21 + sum(pixel * k)) >> 22, clamped to 0..255."""
+    in_size = a.shape[0]
+    if in_size == out_size:
+        return a
+    k, bounds = resample_taps(in_size, out_size)
+    idx = np.minimum(bounds[:, :1].astype(np.int64) + np.arange(k.shape[1])[None, :], in_size - 1)   # (out, width); k is 0 behind count
+    acc = (a[idx] * k.astype(np.int64).reshape(k.shape + (1,) * (a.ndim - 1))).sum(1)
+    return np.clip((acc + (1 << (_RESAMPLE_BITS - 1))) >> _RESAMPLE_BITS, 0, 255)
+
+
+def resample_vertical_first(win_h, win_w, out_h):
+    """Image.resize runs the vertical pass FIRST on a sliver -- more than 100 times as tall as wide, and shrinking vertically; every
+    other image horizontal first. (The rounding to uint8 between the passes makes the order visible from a width of 2 on.)"""
+    return (win_h > 100 * win_w) & (out_h < win_h)
+
+
+def resample_geometry(geometry, frames_shape, out_hw, max_scale=None):
+    """Validate per-frame geometry rows (src_h, src_w, y0, x0, win_h, win_w, flip, 0) against a (N,Hs,Ws,3) container and an output size
+    -> int32 ndarray (N, 8). ValueError naming the first offending frame: a window smaller than 1, a valid extent outside the container,
+    and -- with ``max_scale``, the kernel's limits -- a window more than max_scale times the output along an axis, or a sliver that
+    Pillow resamples vertical pass first (``resample_vertical_first``), which the kernel, horizontal first always, would get other bytes
+    for. Slivers whose horizontal pass cannot change a byte -- one column wide, or as wide as the output -- are accepted: there the
+    order of the passes is invisible."""
+    N, Hs, Ws = int(frames_shape[0]), int(frames_shape[1]), int(frames_shape[2])
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    if OH < 1 or OW < 1:
+        raise ValueError("clip_resample: output size %dx%d" % (OH, OW))
+    g = np.asarray(geometry.cpu() if isinstance(geometry, torch.Tensor) else geometry)
+    if g.shape != (N, 8) or g.dtype.kind not in "iu":
+        raise ValueError("clip_resample: geometry is an integer (N, 8) array with N = %d, got %s %s" % (N, g.dtype, g.shape))
+    g = np.ascontiguousarray(g, dtype=np.int64)
+    checks = (
+        ((np.abs(g) >= 2 ** 30).any(1), "an entry beyond 2^30 (window %d x %d)", (4, 5)),
+        ((g[:, 4] < 1) | (g[:, 5] < 1), "a window of %d x %d", (4, 5)),
+        ((g[:, 0] < 1) | (g[:, 0] > Hs) | (g[:, 1] < 1) | (g[:, 1] > Ws), "a valid extent of %%d x %%d outside its %d x %d container" % (Hs, Ws), (0, 1)),
+    )
+    if max_scale is not None:
+        checks += (((g[:, 4] > max_scale * OH) | (g[:, 5] > max_scale * OW),
+                    "a window of %%d x %%d, more than %d times the %d x %d output" % (max_scale, OH, OW), (4, 5)),
+                   # the order of the passes shows only where the horizontal pass does something between them: not where it is the
+                   # identity (win_w == OW: Pillow skips it), and not on a single column (win_w == 1: every tap row is normalised, so
+                   # the pass copies the column's value, exactly, into every output column)
+                   (resample_vertical_first(g[:, 4], g[:, 5], OH) & (g[:, 5] > 1) & (g[:, 5] != OW),
+                    "a window of %d x %d, over 100 times as tall as wide: Pillow resamples it vertical pass first, the kernel cannot", (4, 5)))
+    for bad, what, cols in checks:
+        if bad.any():
+            n = int(np.argmax(bad))
+            raise ValueError("clip_resample: frame %d has " % n + what % tuple(int(g[n, c]) for c in cols))
+    return g.astype(np.int32)
+
+
+def clip_resample_reference(frames, geometry, out_hw):
+    """uint8 frames (N,Hs,Ws,3) + geometry (N,8) -> uint8 (N,OH,OW,3) on the frames' device: per frame, the window
+    [y0, y0+win_h) x [x0, x0+win_w) of the valid extent (src_h, src_w) -- coordinates outside it replicate the nearest edge -- resized as
+    Pillow's ``crop().resize((OW, OH), BILINEAR)`` does, byte for byte (horizontal pass, rounded to uint8, vertical pass, with
+    ``resample_taps``), then mirrored left-right where flip is set. Integer numpy arithmetic, any window size: the counterpart of
+    ``frames_normalize_reference``, what agrl_clip_resample_u8 is compared with bit for bit."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("clip_resample: frames are uint8 (N,Hs,Ws,3), got %s %s" % (frames.dtype, tuple(frames.shape)))
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    geo = resample_geometry(geometry, frames.shape, (OH, OW)).astype(np.int64)
+    src = frames.detach().cpu().numpy()
+    out = np.empty((src.shape[0], OH, OW, 3), dtype=np.uint8)
+    for n, (sh, sw, y0, x0, wh, ww, flip, _) in enumerate(geo.tolist()):
+        rows = np.clip(y0 + np.arange(wh), 0, sh - 1)
+        cols = np.clip(x0 + np.arange(ww), 0, sw - 1)
+        win = src[n][rows][:, cols].astype(np.int64)                            # (win_h, win_w, 3)
+        if resample_vertical_first(wh, ww, OH):
+            win = _resample_axis(_resample_axis(win, OH).transpose(1, 0, 2), OW).transpose(1, 0, 2)
+        else:
+            win = _resample_axis(win.transpose(1, 0, 2), OW).transpose(1, 0, 2)     # horizontal first, as ImagingResample
+            win = _resample_axis(win, OH)
+        out[n] = win[:, ::-1] if flip else win
+    return torch.from_numpy(out).to(frames.device)
+
+
+def clip_resample(frames, geometry, out_hw, out=None):
+    """The same on the GPU (agrl_clip_resample_u8): ``frames`` uint8 (N,Hs,Ws,3) on the device, channel-last and contiguous;
+    ``geometry`` a HOST integer (N,8) array, validated here (``resample_geometry`` with the kernel's RESAMPLE_MAX_SCALE) and uploaded
+    non-blocking; -> uint8 (N,OH,OW,3) (``out``: written in place when given). One launch, no synchronisation."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("clip_resample: frames are uint8 (N,Hs,Ws,3), got %s" % (
+            "%s %s" % (frames.dtype, tuple(frames.shape)) if isinstance(frames, torch.Tensor) else type(frames)))
+    if not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError("clip_resample: frames must be contiguous on the GPU")
+    if isinstance(geometry, torch.Tensor) and geometry.is_cuda:
+        raise ValueError("clip_resample: geometry is a host array (it is validated before the upload)")
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    if not (1 <= OH <= RESAMPLE_MAX_OUT and 1 <= OW <= RESAMPLE_MAX_OUT):
+        raise ValueError("clip_resample: output size %dx%d, 1..%d each" % (OH, OW, RESAMPLE_MAX_OUT))
+    N, Hs, Ws = frames.shape[:3]
+    geo = torch.from_numpy(resample_geometry(geometry, frames.shape, (OH, OW), RESAMPLE_MAX_SCALE))
+    if out is None:
+        out = torch.empty((N, OH, OW, 3), dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, OH, OW, 3) or out.device != frames.device or not out.is_contiguous():
+        raise ValueError("clip_resample: out must be contiguous uint8 %s on %s" % ((N, OH, OW, 3), frames.device))
+    if N == 0:
+        return out
+    geo_d = geo.pin_memory().to(frames.device, non_blocking=True)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * frames.numel() + 1.0 * out.numel()}
+    with _dev(frames):
+        call("agrl_clip_resample_u8", ptr(frames), ptr(geo_d), ptr(out), N, Hs, Ws, OH, OW, _stream(frames))
+    return out
+
+
+def resample_taps_device(in_size, out_size, device):
+    """agrl_resample_taps_u8: the taps as the GPU computes them -> (k int32 (out, RESAMPLE_TAPS), bounds int32 (out, 2)) on ``device``."""
+    k = torch.empty((int(out_size), RESAMPLE_TAPS), dtype=torch.int32, device=device)
+    bounds = torch.empty((int(out_size), 2), dtype=torch.int32, device=device)
+    with _dev(k):
+        call("agrl_resample_taps_u8", int(in_size), int(out_size), ptr(k), ptr(bounds), _stream(k))
+    return k, bounds
 
 
 def _stem_frames(x, mean, std):

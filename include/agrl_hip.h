@@ -111,6 +111,30 @@ int agrl_stem_split16_u8(const unsigned char* x, const float* table, int layout,
 int agrl_frames_normalize_u8(const unsigned char* x, const float* table, int layout, float* out, int N, int H, int W,
                              agrl_stream_t stream);
 
+/* Resize / crop / flip of decoded frames in front of the stems: the Pillow half of the reference's transforms (GroupResize, and for
+ * training GroupMisAlignAugment, GroupRandomCrop and GroupRandomHorizontalFlip, train_vidreid_xent_htri.py:192-217), BIT-EXACT with
+ * Image.crop(window).resize((OW, OH), BILINEAR) followed by the left-right flip.
+ *   x        : uint8 channel-last frames in a padded container (N, Hs, Ws, 3); any byte alignment
+ *   geometry : device int32 (N, 8) = src_h, src_w, y0, x0, win_h, win_w, flip, 0 per frame. src_h <= Hs, src_w <= Ws: the frame's valid
+ *              extent inside the container -- no byte outside it is ever read. The window [y0, y0+win_h) x [x0, x0+win_w) is an image of
+ *              its own: the filter support ends at the WINDOW's edge, and window coordinates outside the valid extent read the nearest
+ *              valid row / column (edge replication: the two pad cases of the misalign augmentation)
+ *   out      : uint8 (N, OH, OW, 3), OH and OW in 1..512; output columns mirrored where flip != 0
+ * Arithmetic, per axis, horizontal pass first (Pillow's ImagingResample for 8-bit channels): in fp64 scale = in / out, fs = max(scale, 1),
+ * center = (i + 0.5) scale, taps j in [max(int(center - fs + 0.5), 0), min(int(center + fs + 0.5), in)), w = 1 - |(j - center + 0.5) / fs|
+ * (0 from 1 on), divided by their sum, stored as int(0.5 + w 2^22); a pass is (2^21 + sum(pixel k)) >> 22 in int32 clamped to 0..255, with
+ * the result rounded to uint8 between the passes; a pass with in == out is the identity. The kernel derives the taps itself from the
+ * geometry: the host prepares nothing that depends on the sizes. It holds 17 taps per output element -- a downscale of up to 8 per axis,
+ * which the caller checks on its host copy of the geometry; the kernel clamps tap counts, spans and every source index, so it is
+ * memory-safe for any geometry contents (a larger window is resampled from truncated taps). */
+int agrl_clip_resample_u8(const unsigned char* x, const int* geometry, unsigned char* out, int N, int Hs, int Ws, int OH, int OW,
+                          agrl_stream_t stream);
+
+/* The taps above as the device computes them, for one (in, out) pair: k_out int32 (out, 17), zero behind each row's taps, and bounds_out
+ * int32 (out, 2) = (first tap, tap count <= 17; a row with more keeps its first 17, normalised among themselves). A test hook for the
+ * fp64 arithmetic on its own. */
+int agrl_resample_taps_u8(int in, int out, int* k_out, int* bounds_out, agrl_stream_t stream);
+
 /* Implicit-GEMM convolution (1x1 or 3x3, stride 1|2) + folded BN + optional residual + optional
  * ReLU, NHWC in / NHWC out. One call == one (conv, bn[, +residual][, relu]) group of
  * Bottleneck.forward, torchreid/models/vmgn.py:45-65 (and the downsample branch :58-59).
