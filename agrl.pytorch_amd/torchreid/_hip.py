@@ -102,6 +102,12 @@ SIGNATURES = {
     "agrl_graph_propagate": [_p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _i, _i, _i, _p],
     "agrl_pam_pool": [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _p],
     "agrl_pam_combine": [_p, _p, _p, _f, _p, _p, _i, _i, _p],
+    "agrl_pam_pool_train": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _p],
+    "agrl_pam_pool_backward": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _p],
+    "agrl_pam_combine_train": [_p, _p, _p, _p, _p, _i, _i, _p],
+    "agrl_pam_combine_backward": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p],
+    "agrl_col_sum_workspace": [_i, _i],   # returns size_t
+    "agrl_col_sum": [_p, _p, _i, _i, _p, C.c_size_t, _p],
     "agrl_graph_apply": [_p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_graph_tracklet_operand": [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "agrl_graph_finalize_bits": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p],
@@ -181,6 +187,7 @@ def lib():
             fn.restype = _i
         h.agrl_re_ranking_workspace.restype = C.c_size_t
         h.agrl_bn_workspace.restype = C.c_size_t
+        h.agrl_col_sum_workspace.restype = C.c_size_t
         h.agrl_conv_wgrad_workspace.restype = C.c_size_t
         h.agrl_distmat_topk_workspace.restype = C.c_size_t
         h.agrl_bottleneck_seam_packed_bytes.restype = C.c_longlong

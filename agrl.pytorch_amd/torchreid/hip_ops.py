@@ -1196,6 +1196,147 @@ def pam_combine(y, bv, xmean, gamma, want_lp):
     return nodes, nodes_lp
 
 
+PAM_MAXL = 128   # positions a pyramid slice may hold (csrc/pam.hip); also the row length of abar
+
+
+def pam_slices(splits, h):
+    """[(first row, end row)] of the pyramid slices in part order: h // n rows each, remainder rows dropped (ganet.py:387-390)."""
+    return [((h // int(n)) * j, (h // int(n)) * (j + 1)) for n in splits for j in range(int(n))]
+
+
+def pam_pool_train(x, qk, splits):
+    """pam_pool under train(): x (F,h,w,C), qk (F,h,w,2*Cq) fp32 -> xbar, xmean (F,P,C), abar (F,P,128; zero beyond a slice's
+    positions). Always the attention branch: d loss / d gamma is not zero at gamma == 0."""
+    F_, h, w, Cc = x.shape
+    assert tuple(qk.shape[:3]) == (F_, h, w) and qk.shape[3] % 2 == 0
+    P = int(sum(splits))
+    xbar = torch.empty((F_, P, Cc), dtype=torch.float32, device=x.device)
+    xmean = torch.empty((F_, P, Cc), dtype=torch.float32, device=x.device)
+    abar = torch.empty((F_, P, PAM_MAXL), dtype=torch.float32, device=x.device)
+    arr = (C.c_int * len(splits))(*[int(s) for s in splits])
+    with _dev(x):
+        call("agrl_pam_pool_train", ptr(x), ptr(qk), ptr(xbar), ptr(xmean), ptr(abar), F_, h, w, Cc, qk.shape[3] // 2, arr, len(splits),
+             dtype_code(x.dtype), _stream(x))
+    return xbar, xmean, abar
+
+
+def pam_pool_backward(x, qk, dxbar, dxmean, splits, want_abar=False):
+    """Backward of pam_pool_train: dxbar, dxmean (F,P,C) (dxmean = 2 dnode; the 1 / L is the kernel's) -> dx (F,h,w,C),
+    dqk (F,h,w,2*Cq) [, abar (F,P,128) as recomputed on the way]. Formulas: pam_nodes_backward_reference."""
+    F_, h, w, Cc = x.shape
+    P = int(sum(splits))
+    assert tuple(dxbar.shape) == tuple(dxmean.shape) == (F_, P, Cc) and tuple(qk.shape[:3]) == (F_, h, w)
+    dx = torch.empty_like(x)
+    dqk = torch.empty_like(qk)
+    abar = torch.empty((F_, P, PAM_MAXL), dtype=torch.float32, device=x.device)
+    arr = (C.c_int * len(splits))(*[int(s) for s in splits])
+    with _dev(x):
+        call("agrl_pam_pool_backward", ptr(x), ptr(qk), ptr(dxbar), ptr(dxmean), ptr(dx), ptr(dqk), ptr(abar), F_, h, w, Cc, qk.shape[3] // 2,
+             arr, len(splits), dtype_code(x.dtype), _stream(x))
+    return (dx, dqk, abar) if want_abar else (dx, dqk)
+
+
+def pam_combine_train(y, bv, xmean, gamma):
+    """nodes = gamma (y + bv) + 2 xmean with gamma a device tensor (1,) -- the nn.Parameter, never read by the host."""
+    nodes = torch.empty_like(xmean)
+    rows, Cc = xmean.numel() // xmean.shape[-1], xmean.shape[-1]
+    with _dev(xmean):
+        call("agrl_pam_combine_train", ptr(y), ptr(bv), ptr(xmean), ptr(gamma), ptr(nodes), rows, Cc, _stream(xmean))
+    return nodes
+
+
+def col_sum_plan(M):
+    """(row chunks, rows per chunk) of agrl_col_sum / agrl_pam_combine_backward for M rows (csrc/pam.hip: pam_row_chunks)."""
+    chunks = min(64, max(1, M // 32))
+    return chunks, -(-M // chunks)
+
+
+def _col_sum_ws(M, Cc, device):
+    nbytes = int(_hip.lib().agrl_col_sum_workspace(int(M), int(Cc)))
+    return torch.empty((nbytes // 4,), dtype=torch.float32, device=device), nbytes
+
+
+def pam_combine_backward(dnodes, y, bv, gamma):
+    """dnodes, y (rows..,C), bv (C), gamma (1,) device -> dy = gamma dnodes, dxmean = 2 dnodes, dgamma (1,), dbv (C)."""
+    Cc = dnodes.shape[-1]
+    rows = dnodes.numel() // Cc
+    dy, dxmean = torch.empty_like(dnodes), torch.empty_like(dnodes)
+    dgamma = torch.empty((1,), dtype=torch.float32, device=dnodes.device)
+    dbv = torch.empty((Cc,), dtype=torch.float32, device=dnodes.device)
+    ws, nbytes = _col_sum_ws(rows, Cc, dnodes.device)
+    with _dev(dnodes):
+        call("agrl_pam_combine_backward", ptr(dnodes), ptr(y), ptr(bv), ptr(gamma), ptr(dy), ptr(dxmean), ptr(dgamma), ptr(dbv), rows, Cc,
+             ptr(ws), nbytes, _stream(dnodes))
+    return dy, dxmean, dgamma, dbv
+
+
+def col_sum(x2d):
+    """(M,C) fp32 -> (C): column sums in a fixed order (the bias gradient of the stacked query / key conv)."""
+    M, Cc = x2d.shape
+    assert x2d.dtype == torch.float32
+    out = torch.empty((Cc,), dtype=torch.float32, device=x2d.device)
+    ws, nbytes = _col_sum_ws(M, Cc, x2d.device)
+    with _dev(x2d):
+        call("agrl_col_sum", ptr(x2d), ptr(out), M, Cc, ptr(ws), nbytes, _stream(x2d))
+    return out
+
+
+def pam_nodes_backward_reference(x, wq, bq, wk, bk, wv, bv, gamma, splits, dnodes):
+    """ganet's position-attention part nodes and their gradient by the folded algebra the kernels use (csrc/pam.hip, include/
+    agrl_hip.h), in plain torch on the tensors' own device and dtype (float64 in the tests): the value conv is never evaluated per
+    position. x (F,h,w,C) NHWC map, wq / wk (Cq,C), bq / bk (Cq), wv (C,C), bv (C), gamma scalar tensor, dnodes (F,P,C).
+    Per slice (L positions, X its (L,C) rows):
+        A = softmax_rows(Q K^T), abar = mean_p A[p], xbar = X^T abar, xmean = mean_q X[q], node = gamma (Wv xbar + bv) + 2 xmean
+        dgamma += dnode . (Wv xbar + bv), dbv += gamma dnode, dy = gamma dnode, dWv += dy xbar^T, dxbar = Wv^T dy
+        dX += abar dxbar^T + (2 / L) 1 dnode^T, dabar = X dxbar, g = A dabar, dE = A (dabar[q] - g[p]) / L
+        dQ = dE K, dK = dE^T Q, dWq += dQ^T X, dbq += sum_p dQ, dWk += dK^T X, dbk += sum_q dK (identically 0), dX += dQ Wq + dK Wk
+    -> dict: nodes, xbar, xmean (F,P,C), abar (list per part of (F,L)), dx, dxbar (F,P,C), dqk (F,h,w,2*Cq; query first, before the
+    conv's own data gradient), dwq, dbq, dwk, dbk, dwv, dbv, dgamma."""
+    F_, h, w, Cc = x.shape
+    Cq = wq.shape[0]
+    g = gamma.reshape(())
+    q_map = x @ wq.t() + bq
+    k_map = x @ wk.t() + bk
+    slices = pam_slices(splits, h)
+    nodes, xbars, xmeans, abars = [], [], [], []
+    dx_pool = torch.zeros_like(x)                                    # through xbar / xmean only
+    dqk = x.new_zeros((F_, h, w, 2 * Cq))
+    dxbars = []
+    dwv, dbv_, dgamma = torch.zeros_like(wv), torch.zeros_like(bv), g.new_zeros(())
+    for part, (r0, r1) in enumerate(slices):
+        L = (r1 - r0) * w
+        X = x[:, r0:r1].reshape(F_, L, Cc)
+        Q, K = q_map[:, r0:r1].reshape(F_, L, Cq), k_map[:, r0:r1].reshape(F_, L, Cq)
+        A = torch.softmax(Q @ K.transpose(1, 2), dim=2)
+        abar = A.mean(dim=1)                                         # (F, L)
+        xbar = torch.einsum('fq,fqc->fc', abar, X)
+        xmean = X.mean(dim=1)
+        yb = xbar @ wv.t() + bv
+        nodes.append(g * yb + 2 * xmean)
+        xbars.append(xbar), xmeans.append(xmean), abars.append(abar)
+        dn = dnodes[:, part]
+        dgamma = dgamma + (dn * yb).sum()
+        dbv_ = dbv_ + g * dn.sum(0)
+        dy = g * dn
+        dwv = dwv + dy.t() @ xbar
+        dxbar = dy @ wv
+        dxbars.append(dxbar)
+        dX = abar.unsqueeze(2) * dxbar.unsqueeze(1) + (2.0 / L) * dn.unsqueeze(1)
+        dabar = torch.einsum('fqc,fc->fq', X, dxbar)
+        gp = torch.einsum('fpq,fq->fp', A, dabar)
+        dE = A * (dabar.unsqueeze(1) - gp.unsqueeze(2)) / L
+        dQ, dK = dE @ K, dE.transpose(1, 2) @ Q
+        dx_pool[:, r0:r1] += dX.reshape(F_, r1 - r0, w, Cc)
+        dqk[:, r0:r1, :, :Cq] += dQ.reshape(F_, r1 - r0, w, Cq)
+        dqk[:, r0:r1, :, Cq:] += dK.reshape(F_, r1 - r0, w, Cq)
+    dq2, dk2, x2 = dqk[..., :Cq].reshape(-1, Cq), dqk[..., Cq:].reshape(-1, Cq), x.reshape(-1, Cc)
+    return {'nodes': torch.stack(nodes, 1), 'xbar': torch.stack(xbars, 1), 'xmean': torch.stack(xmeans, 1), 'abar': abars,
+            'dxbar': torch.stack(dxbars, 1), 'dx_pool': dx_pool, 'dqk': dqk,
+            'dx': dx_pool + (dq2 @ wq + dk2 @ wk).reshape(x.shape),
+            'dwq': dq2.t() @ x2, 'dbq': dq2.sum(0), 'dwk': dk2.t() @ x2, 'dbk': dk2.sum(0),
+            'dwv': dwv, 'dbv': dbv_, 'dgamma': dgamma}
+
+
 def clip_pool(feats, num_clips, mode="avg"):
     """(T*num_clips, D) fp32 -> (T, D): mean / max over each tracklet's clips. train_vidreid_xent_htri.py:471-476."""
     assert feats.dtype == torch.float32 and feats.dim() == 2 and feats.size(0) % num_clips == 0 and mode in ("avg", "max")

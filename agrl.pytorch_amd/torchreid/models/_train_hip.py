@@ -12,6 +12,8 @@ torch.autograd keeps the graph (so the reference's driver, losses and optimizer 
     BatchNorm2d (train)   agrl_bn_stats -> agrl_bn_apply (normalise + shortcut add + ReLU in one pass); running statistics
                           updated as nn.BatchNorm2d does (momentum 0.1, unbiased variance); backward agrl_bn_backward
     max pooling           agrl_maxpool3x3s2 / agrl_maxpool3x3s2_backward
+    ganet's part nodes    agrl_pam_pool_train / agrl_pam_pool_backward (position attention per pyramid slice, the value conv folded
+                          into one Linear), agrl_pam_combine_train / agrl_pam_combine_backward, agrl_col_sum
 
 Layout: NHWC fp32 between the nodes (the layout of the eval path); NCHW only at the boundary to the stock-torch tail.
 """
@@ -353,6 +355,65 @@ class HipPartPool(torch.autograd.Function):
         return dx1, dx2, None, None
 
 
+class HipPamNodes(torch.autograd.Function):
+    """ganet's position-attention pooling (ganet.py:98-136, :384-400) up to the value conv: map x (F,h,w,C) NHWC and the stacked
+    query / key conv output WITHOUT its bias, qk0 (F,h,w,2*Cq), bias bqk (2*Cq) -> xbar, xmean (F,P,C): agrl_pam_pool_train;
+    backward agrl_pam_pool_backward (dx, dqk) and agrl_col_sum (the bias gradient). fp32 in both train precisions."""
+
+    @staticmethod
+    def forward(ctx, x, qk0, bqk, splits):
+        x = x.contiguous()
+        C2 = qk0.shape[-1]
+        key = (x.device, C2)
+        if key not in ops._UNIT:
+            ops._UNIT[key] = (torch.ones((C2,), dtype=torch.float32, device=x.device), torch.zeros((C2,), dtype=torch.float32, device=x.device))
+        # qk = qk0 + bias on the BatchNorm apply kernel (unit scale: one fma, exactly the rounded sum)
+        qk, _ = ops.bn_apply(qk0.contiguous().view(-1, C2), ops._UNIT[key][0], bqk.detach().contiguous(), None, False)
+        qk = qk.view(qk0.shape)
+        xbar, xmean, _ = ops.pam_pool_train(x, qk, list(splits))
+        ctx.save_for_backward(x, qk)
+        ctx.splits = tuple(int(v) for v in splits)
+        return xbar, xmean
+
+    @staticmethod
+    def backward(ctx, dxbar, dxmean):
+        x, qk = ctx.saved_tensors
+        dx, dqk = ops.pam_pool_backward(x, qk, dxbar.contiguous(), dxmean.contiguous(), list(ctx.splits))
+        dbqk = ops.col_sum(dqk.view(-1, dqk.shape[-1])) if ctx.needs_input_grad[2] else None
+        return dx, dqk, dbqk, None
+
+
+class HipPamCombine(torch.autograd.Function):
+    """nodes = gamma (y + bv) + 2 xmean (ganet.py:394-399 pooled), gamma the module's parameter read on the device."""
+
+    @staticmethod
+    def forward(ctx, y, bv, xmean, gamma):
+        y, xmean = y.contiguous(), xmean.contiguous()
+        ctx.save_for_backward(y, bv, gamma)
+        return ops.pam_combine_train(y, bv.detach().contiguous(), xmean, gamma.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dnodes):
+        y, bv, gamma = ctx.saved_tensors
+        dy, dxmean, dgamma, dbv = ops.pam_combine_backward(dnodes.contiguous(), y, bv.detach().contiguous(), gamma.detach().contiguous())
+        return dy, dbv, dxmean, dgamma.view(gamma.shape)
+
+
+def pam_nodes_train(pam, a, splits):
+    """PAM_Module on every pyramid slice + ``pam(slice) + slice`` average pooled (ganet.py:384-400) under train(): a (F,h,w,C) NHWC
+    -> nodes (F,P,C). One stacked query / key 1x1 conv over the map (shared by the pyramid levels), the attention node, ONE Linear
+    for the value conv (pooling is linear and attention rows sum to one), the combine node. The conv and the Linear follow the
+    calling thread's GEMM arithmetic (hip_train_precision); the attention node is fp32."""
+    F_, h, w, C = a.shape
+    wqk = torch.cat([pam.query_conv.weight, pam.key_conv.weight], 0)
+    bqk = torch.cat([pam.query_conv.bias, pam.key_conv.bias], 0)
+    qk0 = HipConv2d.apply(a, wqk, 1, 0)
+    xbar, xmean = HipPamNodes.apply(a, qk0, bqk, tuple(splits))
+    P = xbar.shape[1]
+    y = linear_train(xbar.view(F_ * P, C), pam.value_conv.weight.view(C, C)).view(F_, P, C)
+    return HipPamCombine.apply(y, pam.value_conv.bias, xmean, pam.gamma)
+
+
 class HipGraphMatrix(torch.autograd.Function):
     """G = mix(rowL1(adj), rowL1(sim(f))), vmgn.py:114-120, :155-166; gradient w.r.t. f through the similarity."""
 
@@ -453,14 +514,16 @@ class HipXent(torch.autograd.Function):
         return dl * go, None, None
 
 
-def graph_layer_train(layer, f, adj):
-    """GraphLayer.forward (vmgn.py:142-172) in train mode (BatchNorm1d over the N*V rows with batch statistics)."""
+def graph_layer_train(layer, f, adj, mask_diag=False, keep=None):
+    """GraphLayer.forward (vmgn.py:142-172) in train mode (BatchNorm1d over the N*V rows with batch statistics). ``mask_diag`` and
+    ``keep`` = 1 are ganet's layer (ganet.py:253-283): self-loops masked out of both graphs, ``input + gamma * h'``; the defaults
+    are vmgn's and gsta's ``(1 - gamma) input + gamma h'``."""
     B, V, C = f.shape
     h = linear_train(f.reshape(B * V, C), layer.linear.weight).view(B, V, C)
-    G = HipGraphMatrix.apply(f, adj, layer.use_pose, layer.learn_graph, False)
+    G = HipGraphMatrix.apply(f, adj, layer.use_pose, layer.learn_graph, mask_diag)
     msg = HipGraphBmm.apply(G, h)
     y = _bn_act(layer.bn, msg.view(B * V, C), None, True, layer.relu.negative_slope).view(B, V, C)
-    return HipAxpby.apply(f, y, 1.0 - layer.gamma, layer.gamma)
+    return HipAxpby.apply(f, y, 1.0 - layer.gamma if keep is None else keep, layer.gamma)
 
 
 def tail_train(model, x4_1, x4_2, adj, B, S):
@@ -545,6 +608,52 @@ def forward_train_gsta(model, x, adj):
                 keep.append(idx)
             keep = torch.LongTensor(keep).to(f.device)
             sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, P, Cf))
+            sf_g = HipAttnPool.apply(sf)
+            sy = linear_train(_bn_act(model.bottleneck, sf_g, None, False), model.classifier.weight)
+        y = linear_train(bn, model.classifier.weight)
+    if model.loss == {'xent'}:
+        return [y, sy] if model.consistent_loss else y
+    if model.loss == {'xent', 'htri'}:
+        return ([y, sy], [f_g, sf_g]) if model.consistent_loss else (y, f_g)
+    raise KeyError('Unsupported loss: {}'.format(model.loss))
+
+
+def forward_train_ganet(model, x, adj):
+    """The sibling ``ganet`` under model.train() on the GPU (reference ganet.py:378-443): gsta's native step with ganet's
+    differences -- position-attention part nodes (pam_nodes_train) instead of the plain part pooling, graph layers with the diagonal
+    masked and the residual form ``input + gamma * h'`` (with the constructor's gamma = 0 the message adds nothing, but its
+    BatchNorm1d still sees the batch and moves its running statistics, as in the reference), the layers' outputs concatenated
+    along the channels in front of the attention pooling, one BNNeck -- and the same one-frame-dropped consistent loss."""
+    import numpy as np
+    B, S, C, H, W = x.shape
+    prec = getattr(model, 'hip_train_precision', 'fp32')
+    if prec not in ('fp32', 'bf16x3'):
+        raise ValueError("hip_train_precision must be 'fp32' or 'bf16x3', got {!r}".format(prec))
+    with ops.f32_split(prec == 'bf16x3'):
+        a = stem_train(model, x.view(B * S, C, H, W))
+        for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
+            for unit in stage:
+                a = bottleneck_train(unit, a)
+        P = model.total_split
+        nodes = pam_nodes_train(model.pam_layer, a, model.total_split_list)
+        Cf = nodes.shape[-1]
+        adj = adj.detach().to(torch.float32).contiguous()
+        outs = [nodes.view(B, S * P, Cf)]
+        for layer in model.graph_layers:
+            outs.append(graph_layer_train(layer, outs[-1], adj, mask_diag=True, keep=1.0))
+        Ct = Cf * len(outs)
+        f = torch.cat(outs, dim=2).view(B, S, P, Ct)
+        f_g = HipAttnPool.apply(f)
+        bn = _bn_act(model.bottleneck, f_g, None, False)
+        sy = sf_g = None
+        if model.consistent_loss:
+            keep = []
+            for _ in range(B):
+                idx = list(range(S))
+                idx.remove(np.random.randint(S))
+                keep.append(idx)
+            keep = torch.LongTensor(keep).to(f.device)
+            sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, P, Ct))
             sf_g = HipAttnPool.apply(sf)
             sy = linear_train(_bn_act(model.bottleneck, sf_g, None, False), model.classifier.weight)
         y = linear_train(bn, model.classifier.weight)

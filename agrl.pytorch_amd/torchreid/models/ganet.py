@@ -14,7 +14,9 @@ What differs from vmgn / gsta (and is what the kernels get flags for):
   * the graph layers' outputs are concatenated with their input along the channel axis (ganet.py:402-405).
 
 CUDA tensors in ``eval()`` run ``_ganet_hip.hip_forward_ganet`` (the vmgn conv kernels, ``agrl_pam_pool``, the graph
-kernels with the mask flag, the attention tail); CPU tensors and train mode use the stock-torch module tree below.
+kernels with the mask flag, the attention tail); CUDA tensors in ``train()`` run ``_train_hip.forward_train_ganet`` (forward
+and backward on the HIP kernels; ``hip_train = False`` or ``AGRL_HIP_TRAIN=0`` turns that off); CPU tensors use the
+stock-torch module tree below.
 """
 from __future__ import absolute_import
 from __future__ import division
@@ -156,6 +158,8 @@ class GANet(nn.Module):
         from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
         _ops.check_precision(self.hip_precision)
         self.hip_static_weights = False
+        self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode forward + backward on the HIP kernels
+        self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')
         self._hip_packs = {}
         # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
         # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
@@ -192,6 +196,12 @@ class GANet(nn.Module):
         if x.dtype == torch.uint8:   # every path below reads fp32 frames: normalise first (hip_ops.clips_to_float), then exactly that path
             from torchreid import hip_ops as _ops
             x = _ops.clips_to_float(x, self.pixel_mean, self.pixel_std)
+        if x.is_cuda and self.training and self.hip_train:
+            if x.dtype != torch.float32:
+                raise TypeError('the native train step takes float32 frames, got {}; set model.hip_train = False for the '
+                                'stock-torch module tree'.format(x.dtype))
+            from torchreid.models._train_hip import forward_train_ganet
+            return forward_train_ganet(self, x, adj)
         B, S, C, H, W = x.size()
         fm = self.featuremaps(x.view(B * S, C, H, W))
         _, c, h, w = fm.shape

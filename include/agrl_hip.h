@@ -453,6 +453,46 @@ int agrl_pam_pool(const void* x, const void* qk, float* xbar, float* xmean, int 
 int agrl_pam_combine(const float* y, const float* bv, const float* xmean, float gamma, float* nodes, void* nodes_lp,
                      int rows, int C, agrl_stream_t stream);
 
+/* ---- the same nodes under train(): forward that keeps what the backward wants, and the backward ---------------------------
+ * Per frame and slice, with X (L, C) the slice, Q = X Wq^T + bq and K = X Wk^T + bk (L, Cq) its rows of the stacked conv map:
+ *   forward   A = softmax_rows(Q K^T)      abar = mean_p A[p, :]      xbar = X^T abar      xmean = mean_q X[q, :]
+ *             y = Wv xbar                  node = gamma (y + bv) + 2 xmean
+ *   backward  given dnode (C):  dgamma += dnode . (y + bv)    dbv += gamma dnode    dy = gamma dnode    dxmean = 2 dnode
+ *             dxbar = Wv^T dy (the Linear node)               dX += abar dxbar^T + (1 / L) 1 dxmean^T
+ *             dabar = X dxbar      g = A dabar                dE[p,q] = A[p,q] (dabar[q] - g[p]) / L
+ *             dQ += dE K           dK += dE^T Q
+ * dX, dQ, dK land in map coordinates and the pyramid levels add into them; rows a level drops receive nothing from it. The
+ * gradient of the key bias is identically zero (it shifts every energy of a row alike). Deterministic: no atomics; the levels
+ * add in level order. torchreid.hip_ops.pam_nodes_backward_reference is this in torch. All tensors fp32 (dtype must be AGRL_F32);
+ * a slice holds at most 128 positions, Cq a multiple of 32, at most 16 parts. */
+
+/* agrl_pam_pool for training: always the attention branch (dgamma is not zero at gamma == 0); also returns
+ * abar (F, P, 128) fp32, zero beyond a slice's L positions. */
+int agrl_pam_pool_train(const float* x, const float* qk, float* xbar, float* xmean, float* abar, int F, int h, int w, int C,
+                        int Cq, const int* splits, int n_splits, int dtype, agrl_stream_t stream);
+
+/* x (F,h,w,C), qk (F,h,w,2*Cq), dxbar (F,P,C), dxmean (F,P,C) (the 1 / L is applied here) -> dx (F,h,w,C), dqk (F,h,w,2*Cq);
+ * abar (F,P,128): recomputed with the attention and written on the way (workspace, equals agrl_pam_pool_train's). Every element
+ * of dx and dqk is written; positions no slice covers get exactly 0. */
+int agrl_pam_pool_backward(const float* x, const float* qk, const float* dxbar, const float* dxmean, float* dx, float* dqk,
+                           float* abar, int F, int h, int w, int C, int Cq, const int* splits, int n_splits, int dtype,
+                           agrl_stream_t stream);
+
+/* agrl_pam_combine with gamma read from device memory (the nn.Parameter; no host read): nodes = gamma (y + bv) + 2 xmean. */
+int agrl_pam_combine_train(const float* y, const float* bv, const float* xmean, const float* gamma, float* nodes, int rows, int C,
+                           agrl_stream_t stream);
+
+/* Its backward: dnodes (rows,C) -> dy = gamma dnodes, dxmean = 2 dnodes (rows,C), dbv (C) = gamma sum_r dnodes,
+ * dgamma (1) = sum_{r,c} dnodes (y + bv). Two-stage column sums in a fixed order; workspace of agrl_col_sum_workspace(rows, C). */
+int agrl_pam_combine_backward(const float* dnodes, const float* y, const float* bv, const float* gamma, float* dy, float* dxmean,
+                              float* dgamma, float* dbv, int rows, int C, void* workspace, size_t workspace_bytes,
+                              agrl_stream_t stream);
+
+/* out[c] = sum_r x[r][c] for x fp32 (M,C): rows in min(64, max(1, M / 32)) chunks, a chunk's rows in row order, then the chunks
+ * in chunk order (the bias gradient of the stacked query / key conv = column sums of dqk). */
+size_t agrl_col_sum_workspace(int M, int C);
+int agrl_col_sum(const float* x, float* out, int M, int C, void* workspace, size_t workspace_bytes, agrl_stream_t stream);
+
 /* ---- attention temporal pooling + BNNeck tail -------------------------------------------------- */
 
 /* sqn[r] = sum_c x[r,c]^2 for R rows of C fp32 (one wavefront per row).
