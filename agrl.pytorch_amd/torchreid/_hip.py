@@ -116,6 +116,9 @@ SIGNATURES = {
     "agrl_graph_linear_mix": [_p, _p, _p, _p, _p, _f, _f, _f, _p, _i, _i, _i, _i, _p],
     "agrl_row_sqnorm": [_p, _p, _i, _i, _i, _p],
     "agrl_attn_pool_bnneck": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "agrl_sta_frame_stats": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "agrl_sta_fuse": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "agrl_linear_bn_relu": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_attn_tail": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "agrl_row_l2_normalize": [_p, _p, _i, _i, _i, _i, _i, _p],
     "agrl_distmat_split16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, C.c_size_t, _p],

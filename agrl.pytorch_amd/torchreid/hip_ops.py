@@ -1928,3 +1928,76 @@ def sgd_step(tensors, chunks, weight_decay, momentum, lr, has_momentum, first_st
     with _dev(tensors):
         call("agrl_sgd_step", *_optim_tables(tensors, chunks), float(weight_decay), float(momentum), float(lr), 1 if has_momentum else 0,
              1 if first_step else 0, 1 if nesterov else 0, 1 if zero_grad else 0, _stream(tensors))
+
+
+# ---- tails of the STA baselines (csrc/sta.hip) --------------------------------------------------------------------------------
+STA_PARTS = 4
+LINEAR_BN_RELU_MAX_M = 32   # AGRL_LINEAR_BN_RELU_MAX_M: the rows of x the kernel's LDS staging holds
+
+
+def sta_bins(h):
+    """[(row0, row1)] of AdaptiveAvgPool2d((4,1)) over h rows: floor(i h / 4) .. ceil((i + 1) h / 4)."""
+    return [((i * h) // STA_PARTS, -((-(i + 1) * h) // STA_PARTS)) for i in range(STA_PARTS)]
+
+
+def sta_frame_stats(fmap):
+    """(F,h,w,C) NHWC map, fp32 or the 16-bit type -> vmean (F,4,C), nsum (F,4), nsq (F,4) fp32: the part means, per bin the sum of the
+    pixels' channel norms, and the sum of their squares over the rows of the bin no later bin starts in. sta.py:213-222."""
+    assert fmap.dim() == 4 and fmap.is_cuda and fmap.is_contiguous() and fmap.dtype in (torch.float32, LP_DTYPE)
+    F_, h, w, Cc = fmap.shape
+    assert h >= STA_PARTS and Cc % 8 == 0 and Cc <= (4096 if fmap.dtype == torch.float32 else 8192), (h, Cc)
+    assert fmap.data_ptr() % 16 == 0
+    vmean = torch.empty((F_, STA_PARTS, Cc), dtype=torch.float32, device=fmap.device)
+    nsum = torch.empty((F_, STA_PARTS), dtype=torch.float32, device=fmap.device)
+    nsq = torch.empty((F_, STA_PARTS), dtype=torch.float32, device=fmap.device)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 3.0 * fmap.numel(), "bytes": fmap.element_size() * fmap.numel() + 4 * vmean.numel()}
+    with _dev(fmap):
+        call("agrl_sta_frame_stats", ptr(fmap), ptr(vmean), ptr(nsum), ptr(nsq), F_, h, w, Cc, dtype_code(fmap.dtype), _stream(fmap))
+    return vmean, nsum, nsq
+
+
+def sta_fuse(vmean, B, S, nsum=None, nsq=None, hw=None):
+    """vmean (B*S,4,C) fp32 -> f_g (B,2C) fp32, t_a (B,S,4) fp32, idx (B,4) int32: per part the first frame attaining the largest
+    temporal attention, cat(mean over parts of the selected means, mean over parts of the attention-weighted sums). With ``nsum`` /
+    ``nsq`` (B*S,4) and the map's ``hw``: sta's scores (the map mode); without: simple_sta's (channel norms of the part means)."""
+    assert vmean.dtype == torch.float32 and vmean.is_cuda and vmean.is_contiguous() and vmean.data_ptr() % 16 == 0
+    assert vmean.dim() == 3 and tuple(vmean.shape[:2]) == (B * S, STA_PARTS) and vmean.shape[2] % 4 == 0 and B > 0 and S > 0
+    Cc = vmean.shape[2]
+    map_mode = nsum is not None
+    if map_mode:
+        assert nsq is not None and hw is not None and hw[0] >= STA_PARTS and hw[1] > 0
+        for t in (nsum, nsq):
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B * S, STA_PARTS) and t.device == vmean.device
+    else:
+        assert nsq is None
+    f_g = torch.empty((B, 2 * Cc), dtype=torch.float32, device=vmean.device)
+    t_a = torch.empty((B, S, STA_PARTS), dtype=torch.float32, device=vmean.device)
+    idx = torch.empty((B, STA_PARTS), dtype=torch.int32, device=vmean.device)
+    h, w = hw if map_mode else (0, 0)
+    with _dev(vmean):
+        call("agrl_sta_fuse", ptr(vmean), ptr(nsum), ptr(nsq), ptr(f_g), ptr(t_a), ptr(idx), B, S, Cc, int(h), int(w),
+             0 if map_mode else 1, _stream(vmean))
+    return f_g, t_a, idx
+
+
+def linear_bn_relu(x, w, scale, shift):
+    """relu(scale * (x w^T) + shift): x (M,K) fp32, w (N,K) fp32 or the 16-bit type, scale / shift (N) fp32 -> (M,N) fp32. The
+    weight-streaming kernel up to LINEAR_BN_RELU_MAX_M rows; above, the tiled GEMM (linear_nobias on operands of the weight's type)
+    and the epilogue in torch."""
+    assert x.dim() == 2 and w.dim() == 2 and x.shape[1] == w.shape[1] and x.dtype == torch.float32 and w.dtype in (torch.float32, LP_DTYPE)
+    assert x.is_cuda and x.is_contiguous() and w.is_contiguous() and w.device == x.device
+    M, K = x.shape
+    Nout = w.shape[0]
+    for t in (scale, shift):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (Nout,) and t.device == x.device
+    if M > LINEAR_BN_RELU_MAX_M:
+        y = linear_nobias(x if w.dtype == torch.float32 else x.to(w.dtype), w)
+        return torch.relu(y * scale + shift)
+    assert K % 4 == 0 and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+    out = torch.empty((M, Nout), dtype=torch.float32, device=x.device)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 2.0 * M * K * Nout, "bytes": w.element_size() * w.numel() + 4 * (x.numel() + out.numel())}
+    with _dev(x):
+        call("agrl_linear_bn_relu", ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(out), M, K, Nout, dtype_code(w.dtype), _stream(x))
+    return out

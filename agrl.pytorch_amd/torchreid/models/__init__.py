@@ -2,8 +2,9 @@
 
 ``vmgn`` -- the model BASELINE.json's north_star names -- and its two siblings that share the kernels (SURVEY.md section 8f
 row 4): the single-branch predecessor ``gsta`` (same GraphLayer) and ``ganet`` (position-attention part nodes, diagonal-masked
-graph layers) are provided by this build; the reference's other sibling architectures are
-out of the hot path.
+graph layers) are provided by this build, and so are the three baselines AGRL is measured against, on the same conv trunk:
+``res50tp`` (``gsta``'s route without graph layers), ``simple_sta`` and ``sta`` (the STA tail of csrc/sta.hip). The reference's
+remaining architectures are out of the hot path.
 """
 from __future__ import absolute_import
 
@@ -14,11 +15,17 @@ import shutil
 from .vmgn import *
 from .gsta import *
 from .ganet import *
+from .res50tp import *
+from .simple_sta import *
+from .sta import *
 
 __model_factory = {
     'vmgn': vmgn,
     'gsta': gsta,
     'ganet': ganet,
+    'res50tp': res50tp,
+    'simple_sta': simple_sta,
+    'sta': sta,
 }
 
 

@@ -527,6 +527,42 @@ int agrl_attn_tail(const float* nodes, const float* gsum, const float* g_scale, 
  * in ascending order and divides once. */
 int agrl_clip_pool(const float* feats, float* out, int T, int n, int D, int mode, agrl_stream_t stream);
 
+/* ---- tails of the STA baselines (sibling models sta / simple_sta) ---------------------------------------- */
+
+/* One pass over a layer-4 map (16-byte loads along C) for STA's spatial attention, torchreid/models/sta.py:213-222:
+ *   map   (F,h,w,C) NHWC of dtype (AGRL_F32 / AGRL_LP16)
+ *   vmean (F,4,C) fp32  part means, AdaptiveAvgPool2d((4,1)) bins: rows floor(i h / 4) .. ceil((i+1) h / 4), every column -- bins
+ *                       overlap when h % 4 != 0; the semantics of agrl_part_pool with splits {4}
+ *   nsum  (F,4)   fp32  sum over a bin's pixels of n_p = sqrt(sum_c map[p,c]^2)
+ *   nsq   (F,4)   fp32  sum of n_p^2 over the rows floor(i h / 4) .. floor((i+1) h / 4) (h for the last part): the rows of bin i that
+ *                       no later bin starts in, so nsq[f,0] + .. + nsq[f,3] is the frame's sum with every pixel counted once
+ * One workgroup per (frame, part), fixed reduction order, no atomics. h >= 4, C % 8 == 0, C <= 8192 (16-bit) / 4096 (fp32): a lane
+ * keeps its channels' sums in registers. sum_c vmean^2 (simple_sta's score) is NOT written here: agrl_sta_fuse forms it in its norm
+ * mode from the vmean it reads anyway, so the route whose vmean comes out of the pool-fused conv needs no extra pass either. */
+int agrl_sta_frame_stats(const void* map, float* vmean, float* nsum, float* nsq, int F, int h, int w, int C, int dtype,
+                         agrl_stream_t stream);
+
+/* Frame selection fused with the weighted temporal sum, one workgroup per tracklet (sta.py:217-238, simple_sta.py:208-215):
+ *   mode AGRL_STA_MAP : s_a[s,p] = (nsum[s,p] / npix_p) / max(sqrt(((nsq[s,0] + nsq[s,1]) + nsq[s,2]) + nsq[s,3]), 1e-12), npix_p the
+ *                       pixel count of bin p of an h x w map;  nsum, nsq (B*S,4) from agrl_sta_frame_stats
+ *   mode AGRL_STA_NORM: s_a[s,p] = sqrt(sum_c vmean[s,p,c]^2);  nsum, nsq, h, w are not read (may be NULL / 0)
+ *   t_a[s,p] = s_a / max(sum_s |s_a|, 1e-12);  idx[p] = the FIRST s attaining max_s t_a[s,p] (torch.argmax's tie rule)
+ *   f_g[b] = cat(mean_p vmean[idx[p],p,:], mean_p sum_s t_a[s,p] vmean[s,p,:])
+ *   vmean fp32 (B*S,4,C) -> f_g fp32 (B,2C), t_a fp32 (B,S,4), idx int32 (B,4). Any S >= 1 with 4 S + 4 floats of LDS; C % 4 == 0. */
+#define AGRL_STA_MAP 0
+#define AGRL_STA_NORM 1
+int agrl_sta_fuse(const float* vmean, const float* nsum, const float* nsq, float* f_g, float* t_a, int32_t* idx, int B, int S, int C,
+                  int h, int w, int mode, agrl_stream_t stream);
+
+/* out = relu(scale * (x w^T) + shift): Linear (no bias) + eval BatchNorm1d folded to scale / shift + ReLU for a handful of rows
+ * (sta.py:150-154 fc1 at M = tracklets). x (M,K) fp32, w (N,K) of w_dtype (AGRL_F32 / AGRL_LP16; products and sums in fp32 either way),
+ * scale / shift (N) fp32, out (M,N) fp32. Weight-streaming: a workgroup owns four rows of w, w crosses HBM once whatever M is, x is
+ * staged in LDS in 256-column slices (two buffers of 32 rows = 64 KB): M <= AGRL_LINEAR_BN_RELU_MAX_M, anything above is rejected
+ * (larger M belongs to agrl_linear_nobias). K % 4 == 0. */
+#define AGRL_LINEAR_BN_RELU_MAX_M 32
+int agrl_linear_bn_relu(const float* x, const void* w, const float* scale, const float* shift, float* out, int M, int K, int N,
+                        int w_dtype, agrl_stream_t stream);
+
 /* ---- distance matrix + ranking ------------------------------------------------------------------ */
 
 /* y[r,:C] = x[r,:] / max(||x[r,:]||_2, 1e-12)  (F.normalize p=2), x fp32 (R,C) -> y out_dtype with row
