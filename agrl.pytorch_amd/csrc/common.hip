@@ -60,6 +60,7 @@ static AgrlOpts load_opts() {
     o.split16_ns = opt_int("AGRL_SPLIT16_NS");
     o.stem_xcd_map = opt_int("AGRL_STEM_XCD_MAP");
     o.stem_split_lds = opt_int("AGRL_STEM_SPLIT_LDS");
+    o.stem_regpool = opt_int("AGRL_STEM_REGPOOL");
     o.conv3x3_fat_pb = opt_int("AGRL_CONV3X3_FAT_PB");
     o.conv3x3_half = opt_int("AGRL_CONV3X3_HALF");
     o.conv3x3_half_stagger = opt_int("AGRL_CONV3X3_HALF_STAGGER");

@@ -10,7 +10,11 @@
 //   patch 39x40x4 bf16 (12.5 KB) + packed weights 64 x 240 bf16 (30 KB, LDS-DMA)      -> LDS
 //   conv tile 17x17 = 289 positions x 64 ch: 19 position fragments over 8 waves, 7 k-steps, +bias, ReLU
 //   -> bf16 conv tile in LDS (overlaying patch+weights) -> 3x3/2 max -> NHWC store (128 B per pooled pixel)
+// Frames whose pooled row is 17 .. 32 wide (256 x 128 among them) take stem_regpool_kernel below instead (AGRL_STEM_REGPOOL): the same
+// contraction with the fragments laid out so that the pool is taken in registers; bit-identical outputs.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "stem_dev.h"
 
@@ -187,7 +191,230 @@ __global__ __launch_bounds__(NTH, 4) void stem_mfma_kernel(const TIN* __restrict
         if constexpr (!SPLIT) __syncthreads();  // the conv tile is consumed: the next patch may overwrite it
     }
 }
+
+// ---- register-pool form: the 3x3/2 maximum is taken on the fp32 accumulators, no conv tile goes through LDS ----------------------
+// a -> round16(relu(a + b)) is non-decreasing, so max over a window of round16(relu(acc + b)) = round16(relu(max(acc) + b)) bit for bit
+// (and a NaN still wins: every maximum here is the NaN-propagating one). Each conv position is the same 7 k-steps r = 0..6 of the same
+// MFMA on the same operands as in stem_mfma_kernel, so the outputs are the conv-tile kernel's.
+//
+// Mapping (stem_dev.h, namespace stem_rp): a position fragment = 16 adjacent pooled columns px = 16 G + (lane & 15) of ONE conv row at ONE
+// column phase (conv column 2 px or 2 px + 1); lanes >> 4 pick 4 channels per channel fragment as before. A wave owns two pooled rows of
+// the tile and does column group 0 for both, then group 1. For a pooled row it sweeps conv rows 2 py and 2 py + 1 at both phases (4
+// position x 4 channel fragments x 7 k-steps). The window's third row 2 py - 1 is the previous pooled row's 2 py + 1, carried in registers
+// (column-maxed, 16 values); it is swept once at the top of the wave's strip: 8.75 MFMAs per pooled pixel where the conv tile took 10.5.
+// The third column 2 px - 1 is the left neighbour's odd phase: a DPP row_shr:1 inside the 16-lane row; lane 0 of group 1 takes group 0's
+// lane 15, which the wave left in a 1 280-byte LDS slot of its own (20 ds_write_b128 + 20 ds_read_b128 per wave and tile beside 308
+// operand reads; kept in registers across group 1's sweep the hand-over spilt). Conv row / column -1 and rows / columns past the conv map
+// enter no maximum (-inf). Then once per pooled value: + bias, ReLU, one RNE rounding; two v_permlane16_swap per channel-fragment pair
+// give each lane 8 adjacent channels, stored as 16 bytes.
+//
+// Patch: [39][134][4] 16-bit, plain row-major (row stride 1072 B). Lane (f, g) of a fragment reads 16 B at pixel 4 (16 G + f) + 2 phase +
+// 2 g: its 16-byte slot index is 2 f + g + const. A ds_read_b128 is served in groups of 16 lanes holding f in {0-3, 12-15} at chunk g and
+// f in {4-11} at chunk g + 1 (or the converse): the first set lands on the 8 slots of one parity mod 16, the second on the other
+// parity's 8 -- 0 bank conflicts, with no swizzle. The weight reads are stem_mfma_kernel's (conflict-free, stem_dev.h).
+// LDS 41 808 + 30 720 + 256 + 5 120 = 77 904 B: two 256-thread workgroups per CU, two waves per SIMD, so the register budget is 256.
+namespace rp = stem_rp;
+
+__device__ __forceinline__ float fmax_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float old, float src) {  // lanes whose source lane lies outside the 16-lane row keep ``old``
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), CTRL, 0xf,
+                                                                  0xf, false));
+}
+constexpr int DPP_ROW_SHR1 = 0x111;
+
+// NR conv rows (patch rows 2 i + r) x both column phases x 64 channels: acc[i][phase][channel fragment]
+template <int NR>
+__device__ __forceinline__ void rp_sweep(const unsigned char* xb, const unsigned char* wb, f32x4_t (&acc)[NR][2][4]) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) acc[i][p][a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // operands of k-step r + 1 are requested before the MFMAs of k-step r; the scheduling fence keeps the compiler from requesting
+    // further ahead (at 16 registers a k-step, it spilt)
+    uint4 wf[2][4], xf[2][NR][2];
+    auto fetch = [&](int r, uint4 (&w)[4], uint4 (&xx)[NR][2]) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) w[a] = *reinterpret_cast<const uint4*>(wb + a * 16 * WROW_BYTES + r * 64);
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) xx[i][p] = *reinterpret_cast<const uint4*>(xb + (2 * i + r) * rp::ROW_BYTES + p * 16);
+    };
+    fetch(0, wf[0], xf[0]);
+#pragma unroll
+    for (int r = 0; r < 7; ++r) {
+        if (r < 6) fetch(r + 1, wf[(r + 1) & 1], xf[(r + 1) & 1]);
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int a = 0; a < 4; ++a) acc[i][p][a] = mfma_lp16_16x16x32(wf[r & 1][a], xf[r & 1][i][p], acc[i][p][a]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// maximum over conv columns 2 px - 1, 2 px, 2 px + 1 of one conv row: h = max(even, odd, left neighbour's odd). Lane 0 of each 16-lane
+// row has no left neighbour in its fragment: in group 0 that is conv column -1 (-inf); in group 1 it is group 0's lane 15, which group 0
+// left in ``edge`` (this wave's 256-byte LDS slot of the conv row: [lane >> 4][16 floats]) -- same wave, program order, no barrier.
+template <int GQ>
+__device__ __forceinline__ void rp_row_max(const f32x4_t (&even)[4], f32x4_t (&odd)[4], float* edge, int frow, bool odd_all_in,
+                                           bool odd_in, f32x4_t (&h)[4]) {
+    if (!odd_all_in) {  // a conv map narrower than 64: columns 2 px + 1 >= CW enter no maximum
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) odd[a][j] = odd_in ? odd[a][j] : -INFINITY;
+    }
+    f32x4_t first[4];
+    if constexpr (GQ == 0) {
+        if (frow == 15) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) *reinterpret_cast<f32x4_t*>(edge + 4 * a) = odd[a];
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) first[a] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    } else {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) first[a] = *reinterpret_cast<const f32x4_t*>(edge + 4 * a);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            h[a][j] = fmax_nan(fmax_nan(even[a][j], odd[a][j]), dpp_mov<DPP_ROW_SHR1>(first[a][j], odd[a][j]));
+}
+
+template <typename TIN, typename... EX>
+__global__ __launch_bounds__(rp::NTH, 2) void stem_regpool_kernel(const TIN* __restrict__ x, const unsigned char* __restrict__ wpk,
+                                                                   const float* __restrict__ bias, lp16_t* __restrict__ out, int H,
+                                                                   int W, int CH, int CW, int PH, int PW, int tiles_h, int ntiles,
+                                                                   int xcd_map, EX... ex) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[rp::PATCH_BYTES + W_BYTES + 256 + rp::EDGE_BYTES];
+    unsigned char* s_patch = smem;
+    unsigned char* s_w = smem + rp::PATCH_BYTES;
+    float* s_bias = reinterpret_cast<float*>(smem + rp::PATCH_BYTES + W_BYTES);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = gridDim.x;
+
+    weights_to_lds(wpk, s_w, wave, lane, rp::NWV);  // once per workgroup
+    if (tid < 64) s_bias[tid] = bias[tid];
+    rp::PatchPrefetch<TIN, EX...> pre;
+    constexpr int NPASS_RP = decltype(pre)::NPASS;
+    const int frow = lane & 15, g = lane >> 4;
+    // this lane's patch slice of the strip's first conv row (tile row 4 wave) at filter row 0, group 0, even phase; its weight slice
+    const unsigned char* xlane = s_patch + 8 * wave * rp::ROW_BYTES + (4 * frow + 2 * g) * 8;
+    const unsigned char* wlane = s_w + frow * WROW_BYTES + g * 16;
+    // group 0's lane-15 odd phase of this wave's 5 conv rows, for lane 0 of group 1: [wave][conv row][g][16 floats]
+    float* s_edge = reinterpret_cast<float*>(smem + rp::PATCH_BYTES + W_BYTES + 256) + (wave * (2 * rp::RPW + 1) * 4 + g) * 16;
+
+    // tile order: stem_mfma_kernel's (frame n on XCD n mod 8, whose G / 8 workgroups walk its frames' tiles together)
+    const int nframes = ntiles / tiles_h;
+    const bool xmap = xcd_map && (G & 7) == 0 && nframes >= 8;
+    const int xcd = blockIdx.x & 7;
+    const int qstep = xmap ? (G >> 3) : G;
+    const int qlimit = xmap ? ((nframes - xcd + 7) >> 3) * tiles_h : ntiles;
+    auto tile_of = [&](int q) {
+        if (!xmap) return q;
+        const int fl = q / tiles_h;
+        return (xcd + 8 * fl) * tiles_h + (q - fl * tiles_h);
+    };
+    int q = xmap ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (q < qlimit) pre.load(x, H, W, rp::tile_at(tile_of(q), tiles_h), ex...);
+    for (; q < qlimit; q += qstep) {
+        const Tile t = rp::tile_at(tile_of(q), tiles_h);
+        // ---- this tile's pixels (requested one tile ago) -> 16-bit patch in LDS
+        pre.normalize(ex...);  // uint8 frames: the table gather, here so that bytes and values are never both held across the sweeps
+        int tw = tid;
+        asm volatile("" : "+v"(tw));  // LDS addresses per tile, not hoisted
+#pragma unroll
+        for (int i = 0; i < NPASS_RP; ++i) {
+            const int e = tw + rp::NTH * i;
+            if ((i + 1) * rp::NTH <= rp::IT * rp::PWP || e < rp::IT * rp::PWP) {  // only the last pass is partial
+                uint2 u;
+                u.x = pack_lp16x2(pre.pv[i][0], pre.pv[i][1]);
+                u.y = (uint32_t)f32_to_lp16(pre.pv[i][2]);
+                *reinterpret_cast<uint2*>(s_patch + e * 8) = u;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first tile: the weight DMA (invisible to the compiler) has landed
+        __syncthreads();
+        if (q + qstep < qlimit) pre.load(x, H, W, rp::tile_at(tile_of(q + qstep), tiles_h), ex...);
+
+        const int ph_w = t.ph0 + rp::RPW * wave;  // the strip's first pooled row
+        if (ph_w < PH) {
+            const bool odd_all_in = CW >= 4 * rp::MAX_PW;
+            auto group = [&](auto gq_c) {
+                constexpr int GQ = decltype(gq_c)::value;
+                const unsigned char* xg = xlane + GQ * 512;
+                const int px = 16 * GQ + frow;
+                const bool odd_in = 2 * px + 1 < CW;
+                f32x4_t carry[4];
+                {   // conv row 2 ph_w - 1: only its column maxima are kept
+                    f32x4_t acc[1][2][4];
+                    rp_sweep<1>(xg, wlane, acc);
+                    rp_row_max<GQ>(acc[0][0], acc[0][1], s_edge, frow, odd_all_in, odd_in, carry);
+                    if (ph_w == 0) {  // conv row -1
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) carry[a] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                    }
+                }
+#pragma unroll
+                for (int sp = 0; sp < rp::RPW; ++sp) {
+                    const int ph = ph_w + sp;
+                    if (ph < PH) {
+                        f32x4_t acc[2][2][4], ha[4], hb[4];
+                        rp_sweep<2>(xg + (4 * sp + 2) * rp::ROW_BYTES, wlane, acc);
+                        rp_row_max<GQ>(acc[0][0], acc[0][1], s_edge + (2 * sp + 1) * 64, frow, odd_all_in, odd_in, ha);
+                        rp_row_max<GQ>(acc[1][0], acc[1][1], s_edge + (2 * sp + 2) * 64, frow, odd_all_in, odd_in, hb);
+                        if (2 * ph + 1 >= CH) {  // odd conv height: the last pooled row's window has two rows
+#pragma unroll
+                            for (int a = 0; a < 4; ++a) hb[a] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                        }
+                        // pooled pixel (ph, px): channels 16 a + 4 g + j
+                        uint32_t pk[4][2];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            const float4 bv = *reinterpret_cast<const float4*>(s_bias + a * 16 + g * 4);
+                            float v[4];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) v[j] = fmax_nan(fmax_nan(carry[a][j], ha[a][j]), hb[a][j]);
+                            carry[a] = hb[a];
+                            pk[a][0] = pack_lp16x2(relu_nan(v[0] + bv.x), relu_nan(v[1] + bv.y));
+                            pk[a][1] = pack_lp16x2(relu_nan(v[2] + bv.z), relu_nan(v[3] + bv.w));
+                        }
+                        // rows of 16 lanes g and g ^ 1 trade halves: afterwards lane g holds channel fragment 2 k + (g & 1), channels
+                        // 8 (g >> 1) .. + 7 of it, for k = 0, 1
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+                            const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(pk[2 * k][0], pk[2 * k + 1][0], false, false);
+                            const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(pk[2 * k][1], pk[2 * k + 1][1], false, false);
+                            if (px < PW) {
+                                const int ch = (2 * k + (g & 1)) * 16 + (g >> 1) * 8;
+                                *reinterpret_cast<uint4*>(out + (((size_t)t.n * PH + ph) * PW + px) * 64 + ch) =
+                                    make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                            }
+                        }
+                    }
+                }
+            };
+            group(std::integral_constant<int, 0>{});
+            group(std::integral_constant<int, 1>{});
+        }
+        __syncthreads();  // every wave is done with the patch: the next tile's may be written
+    }
+}
 }  // namespace
+
+// what an unset AGRL_STEM_REGPOOL selects: the register-pool form (step 3.449 against 3.489 ms, four alternated pairs: DESIGN.md 5.4)
+constexpr bool STEM_REGPOOL_DEFAULT = true;
 
 template <typename TIN, typename... EX>
 static int launch_stem_mfma(const char* who, const TIN* x, const void* w_packed, const float* bias, void* out, int N, int H, int W,
@@ -197,6 +424,18 @@ static int launch_stem_mfma(const char* who, const TIN* x, const void* w_packed,
     if (stem_shape(who, N, H, W, PT, PT, &s)) return 1;
     AGRL_CHECK_ARG((((uintptr_t)w_packed) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)out) & 15) == 0,
                    "%s: misaligned pointer", who);
+    // AGRL_STEM_REGPOOL: the register-pool form takes every frame whose pooled row is 17 .. 32 wide (W 65 .. 128), any height
+    const int regpool = agrl_opts().stem_regpool;
+    if ((agrl_opt_set(regpool) ? regpool != 0 : STEM_REGPOOL_DEFAULT) && s.PW >= stem_rp::MIN_PW && s.PW <= stem_rp::MAX_PW) {
+        StemShape r;
+        if (stem_shape(who, N, H, W, stem_rp::RT, stem_rp::MAX_PW, &r)) return 1;
+        const unsigned launch_rp = (unsigned)(r.grid < 512 ? r.grid : 512);  // two persistent workgroups per CU (76 KB of LDS each)
+        hipLaunchKernelGGL((stem_regpool_kernel<TIN, EX...>), dim3(launch_rp), dim3(stem_rp::NTH), 0, (hipStream_t)stream, x,
+                           (const unsigned char*)w_packed, bias, (lp16_t*)out, H, W, r.CH, r.CW, r.PH, r.PW, r.tiles_h, r.grid,
+                           agrl_opts().stem_xcd_map != 0, ex...);
+        AGRL_CHECK_LAUNCH(who);
+        return 0;
+    }
     const int wgs = 512;  // two persistent workgroups per CU (67 KB of LDS each)
     const unsigned launch = (unsigned)(s.grid < wgs ? s.grid : wgs);
     if (agrl_opts().stem_split_lds != 0)
