@@ -698,14 +698,14 @@ __global__ __launch_bounds__(64 * NWV) void graph_apply_stream_kernel(const floa
 // ---------------------------------------------------------------------------------------------------
 // Graph + P = G f of ONE TRACKLET PER WORKGROUP (many tracklets per GPU: B >= 128, so that one workgroup per tracklet fills
 // the chip): the whole HBM-bound part of the commuted GraphLayer in one launch, no Gram partials and no G round trip.
-//   1  Gram: wave w streams channels [w C/4, (w+1) C/4) of the tracklet's V rows straight into exact-fp32 MFMAs (lane = row
+//   1  Gram: wave w streams channels [w C/8, (w+1) C/8) of the tracklet's V rows straight into exact-fp32 MFMAs (lane = row
 //      i16 of a 16-row fragment, k-group kg: one 16-byte load per fragment and 16 channels feeds four k-steps of the ten
-//      fragment pairs I <= J); the four wave partials meet in LDS and are added in wave order (deterministic);
+//      fragment pairs I <= J); the GT_WAVES = 8 wave partials meet in LDS and are added in wave order (deterministic);
 //   2  graph: d2 -> sim -> row-L1 normalise -> mix with the pose graph (graph_finalize_kernel's arithmetic), into LDS;
 //   3  P = G f: the streaming message pass of graph_apply_stream_kernel over the tracklet's channels, 64 per wave and step --
 //      f comes a second time, out of the memory-side cache (458 KB per tracklet, just read).
 // f crosses HBM once per tracklet (V C 4 bytes), P leaves once. The Gram is summed in a different order than the
-// slice-partial form (4 wave partials of C/4 channels, not 16 slices of 128): the graph agrees to fp32 roundoff.
+// slice-partial form (8 wave partials of C/8 channels, not 16 slices of 128): the graph agrees to fp32 roundoff.
 // out[b][e] = sum over the nz slice partials, z ascending
 __global__ __launch_bounds__(256) void gram_sum_kernel(const float* __restrict__ part, int nz, float* __restrict__ out, int vv, size_t total) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;

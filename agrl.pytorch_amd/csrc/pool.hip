@@ -368,7 +368,12 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const float* __restrict_
         for (int i = 0; i < 8; ++i) v[i] = i0 + i < n ? src[(size_t)(i0 + i) * D] : 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            if (i0 + i < n) acc = mode ? __builtin_elementwise_maximum(acc, v[i]) : acc + v[i];  // IEEE-754-2019 maximum: a NaN clip stays a NaN (fmaxf drops it)
+            if (i0 + i < n) {
+                // torch.max over the clips: a later clip replaces the running maximum only if it is greater or a NaN, so a NaN clip
+                // stays a NaN (fmaxf drops it) and among equal maxima the first stands (-0 before +0 stays -0; IEEE maximum picks +0)
+                if (mode) acc = (v[i] > acc || v[i] != v[i]) ? v[i] : acc;
+                else acc = acc + v[i];
+            }
     }
     out[(size_t)t * D + c] = mode ? acc : acc / (float)n;
 }

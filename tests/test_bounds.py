@@ -546,3 +546,389 @@ def test_graph_matrix_backward_reference_accepts_the_fp32_formulas(cfg):
     for fault in ({"diag_gradient": True}, {"scale_one": True}):
         with pytest.raises(AssertionError):
             check_rounded(emulate(**fault), exact, zero, 0, F32, slack=slack, name="graph matrix backward, fault")
+
+
+# ---- tests/graph_ref.py: the float64 references of the eval GraphLayer and the attention tail ------------------------------------
+# Each helper against the kernel's stated arithmetic stepped in torch fp32 (accepted, and within two orders of the bound:
+# worst > 0.01) and against seeded faults (rejected, at the reported coordinate where check_rounded can name it).
+import graph_ref as GR
+
+
+def _old_graph_matrix_backward_ref(gram_part, dG, use_pose, mask_diag=False):
+    """graph_matrix_backward_ref as it stood before its stages up to Shat moved to graph_ref.similarity_chain."""
+    u = R.U32
+    gp = gram_part.double()
+    B, nz, V, _ = gp.shape
+    g, a = gp.sum(1), nz * u * gp.abs().sum(1)
+    n, an = torch.diagonal(g, dim1=1, dim2=2), torch.diagonal(a, dim1=1, dim2=2)
+    eye = torch.eye(V, dtype=torch.bool).view(1, V, V)
+    D2 = n[:, :, None] + n[:, None, :] - 2 * g
+    eD2 = an[:, :, None] + an[:, None, :] + 2 * a + 2 * u * (n[:, :, None] + n[:, None, :] + 2 * g.abs())
+    eD2 = eD2.masked_fill(eye, 0.0)
+    live = (D2 > 1e-12) & ~eye
+    D = D2.clamp(min=1e-12).sqrt()
+    eD = eD2 / (2 * D) + u * D
+    S = 2 / (torch.exp(D) + 1)
+    h = S * (1 - S / 2)
+    eS = h * eD + 4 * u * S
+    if mask_diag:
+        S, h, eS = S.masked_fill(eye, 0.0), h.masked_fill(eye, 0.0), eS.masked_fill(eye, 0.0)
+    t = -(-V // 64) + 6
+    r = S.sum(2, keepdim=True)
+    er = eS.sum(2, keepdim=True) + t * u * r
+    Sh = S / r
+    eSh = Sh * (eS / S.clamp(min=1e-300) + er / r + u)
+    x = dG.double() * (0.5 if use_pose else 1.0)
+    c = (x * Sh).sum(2, keepdim=True)
+    ec = (x.abs() * eSh).sum(2, keepdim=True) + t * u * (x * Sh).abs().sum(2, keepdim=True)
+    dS = (x - c) / r
+    edS = (ec + u * (x.abs() + c.abs())) / r + dS.abs() * (er / r + u)
+    dD = -h * dS
+    edD = dS.abs() * ((1 - S).abs() * eS + 3 * u * h) + h * edS + u * dD.abs()
+    E = torch.where(live, dD / (2 * D), torch.zeros_like(D))
+    eE = torch.where(live, edD / (2 * D) + E.abs() * (eD / D + 2 * u), torch.zeros_like(D))
+    T = E + E.transpose(1, 2)
+    eT = eE + eE.transpose(1, 2) + u * T.abs()
+    rs = T.sum(2)
+    ers = eT.sum(2) + t * u * T.abs().sum(2)
+    M = 2 * (torch.diag_embed(rs) - T)
+    eM = 2 * (torch.diag_embed(ers) + eT) + u * M.abs()
+    return M, eM, live
+
+
+def _gram_partials(f):
+    """agrl_graph_gram's output shape: 128-channel slice partials (B, C / 128, V, V), fp32."""
+    return torch.stack([torch.bmm(f[:, :, z:z + 128], f[:, :, z:z + 128].transpose(1, 2)) for z in range(0, f.shape[-1], 128)], 1)
+
+
+@pytest.mark.parametrize("mask_diag", [False, True])
+@pytest.mark.parametrize("use_pose", [False, True])
+def test_graph_matrix_backward_reference_is_unchanged_by_the_shared_chain(use_pose, mask_diag):
+    g = torch.Generator().manual_seed(11)
+    f = torch.rand((2, 1, 256), generator=g) * 0.2 + 0.05 * torch.randn((2, 28, 256), generator=g)
+    gp, dG = _gram_partials(f), torch.randn((2, 28, 28), generator=g)
+    for new, old in zip(R.graph_matrix_backward_ref(gp, dG, use_pose, mask_diag), _old_graph_matrix_backward_ref(gp, dG, use_pose, mask_diag)):
+        assert torch.equal(new, old)
+
+
+def _finalize_fp32(gp, adj, use_pose, learn_graph, mask_diag, norms=None):
+    """graph_finalize_kernel step by step in fp32. ``norms``: squared norms from another sum than the Gram diagonal (a fault: the
+    diagonal distance becomes fp32 cancellation noise instead of 0)."""
+    B, nz, V, _ = gp.shape
+    eye = torch.eye(V, dtype=torch.bool)
+    if learn_graph:
+        gs = torch.zeros((B, V, V))
+        for z in range(nz):
+            gs = gs + gp[:, z]
+        n = torch.diagonal(gs, dim1=1, dim2=2) if norms is None else norms
+        d2 = ((n[:, None, :] + n[:, :, None]) - 2 * gs).clamp(min=1e-12)
+        sim = 2 / (torch.exp(torch.sqrt(d2)) + 1)
+        if mask_diag:
+            sim = sim.masked_fill(eye, 0.0)
+        Sh = sim / sim.abs().sum(2, keepdim=True).clamp(min=1e-12)
+    if use_pose:
+        a = adj.masked_fill(eye, 0.0) if mask_diag else adj
+        A = a / a.abs().sum(2, keepdim=True).clamp(min=1e-12)
+        return (A + Sh) / 2 if learn_graph else A
+    return Sh
+
+
+def _graph_inputs(B, V, C, seed):
+    """The well-conditioned node features of the GPU suite: independent rows, |f|^2 ~ 8, d2 ~ 16."""
+    g = torch.Generator().manual_seed(seed)
+    f = torch.randn((B, V, C), generator=g) * 4 / (2 * C) ** 0.5
+    adj = (torch.rand((B, V, V), generator=g) > 0.5).float()
+    adj[0, min(3, V - 1)] = 0                          # an all-zero adjacency row
+    return f, adj
+
+
+@pytest.mark.parametrize("cfg", [(3, 56, 256, True, True, False), (2, 20, 128, False, True, False), (2, 33, 128, True, True, True),
+                                 (2, 28, 512, True, False, False), (2, 1, 128, True, True, True)])
+def test_graph_matrix_reference_accepts_the_fp32_formulas_and_rejects_seeded_faults(cfg):
+    B, V, C, use_pose, learn_graph, mask_diag = cfg
+    f, adj = _graph_inputs(B, V, C, V + C)
+    gp = _gram_partials(f)
+    exact, slack = GR.graph_matrix_ref(gp, adj, use_pose, learn_graph, mask_diag)
+    packed, _ = GR.graph_matrix_ref(gp, _pack_bits(adj), use_pose, learn_graph, mask_diag)
+    assert torch.equal(packed, exact), "the bit-packed adjacency unpacks to the same graph"
+    zero = torch.zeros_like(exact)
+    assert bool((slack <= 128 * R.U32 * exact.abs()).all()), "the reference alone is within 128 u |G| on these inputs"
+    got = _finalize_fp32(gp, adj, use_pose, learn_graph, mask_diag)
+    worst, _ = check_rounded(got, exact, zero, 0, F32, slack=slack, name="graph matrix")
+    if V == 1:
+        assert float(exact.abs().max()) == 0.0       # the one node masked out on both halves: 0 / clamp
+        return
+    assert worst > 0.01, "the propagated bound is within two orders of what fp32 does"
+    if learn_graph:
+        bad = got.clone()
+        bad[1, 2, 5] *= 1 + 2.0 ** -12               # one off-diagonal entry: 2^12 u, against a slack of at most 128 u
+        with pytest.raises(AssertionError, match=r"at \(1, 2, 5\)"):
+            check_rounded(bad, exact, zero, 0, F32, slack=slack, name="graph matrix, one entry scaled")
+        # ... which a 5e-4 max-normalised bar does not see
+        assert float((bad.double() - exact).abs().max() / exact.abs().max()) < 5e-4
+        if not mask_diag:
+            noisy = _finalize_fp32(gp, adj, use_pose, learn_graph, mask_diag, norms=(f * f).sum(2))
+            with pytest.raises(AssertionError):
+                check_rounded(noisy, exact, zero, 0, F32, slack=slack, name="graph matrix, diagonal distance from cancellation noise")
+    if use_pose and not learn_graph:
+        bad = _finalize_fp32(gp, adj.transpose(1, 2).contiguous(), True, False, mask_diag)
+        with pytest.raises(AssertionError):
+            check_rounded(bad, exact, zero, 0, F32, slack=slack, name="adjacency transposed")
+
+
+def _pack_bits(adj):
+    """The bit-packed adjacency (hip_ops.adjacency_pack_host's layout) without importing the package."""
+    a = adj.numpy() != 0
+    B, V, _ = a.shape
+    W = (V + 31) // 32
+    pad = np.zeros((B, V, W * 32), dtype=bool)
+    pad[:, :, :V] = a
+    words = (pad.reshape(B, V, W, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=3).astype(np.uint32)
+    return torch.from_numpy(words.view(np.int32).copy())
+
+
+def test_tracklet_gram_reference_accepts_eight_wave_partials():
+    f, adj = _graph_inputs(2, 20, 512, 5)
+    C = f.shape[-1]
+    cq = C // GR.GT_WAVES
+    gram = torch.zeros((2, 20, 20))
+    for w in range(GR.GT_WAVES):                      # wave partials of C / 8 channels, added in wave order
+        part = torch.zeros((2, 20, 20))
+        for c in range(w * cq, (w + 1) * cq, 4):
+            part = (part.double() + torch.bmm(f[:, :, c:c + 4].double(), f[:, :, c:c + 4].double().transpose(1, 2))).float()
+        gram = gram + part
+    exact, bound = GR.tracklet_gram_ref(f)
+    zero = torch.zeros_like(exact)
+    worst, _ = check_rounded(gram, exact, zero, 0, F32, slack=bound, name="tracklet gram")
+    assert worst > 0.01
+    bad = gram - torch.bmm(f[:, :, -4:], f[:, :, -4:].transpose(1, 2))       # the last MFMA step of the last wave dropped
+    with pytest.raises(AssertionError):
+        check_rounded(bad, exact, zero, 0, F32, slack=bound, name="tracklet gram, last step dropped")
+    # the finalize propagation on this Gram: the fp32 graph of the emulated Gram is inside it
+    G, slack = GR.graph_matrix_ref(None, adj, True, True, False, gram=(exact, bound))
+    got = _finalize_fp32(gram[:, None], adj, True, True, False)
+    check_rounded(got, G, zero, 0, F32, slack=slack, name="tracklet graph")
+    P, pmag, n_acc = GR.apply_ref(got, f)
+    worst, _ = check_rounded(torch.bmm(got, f), P, pmag, n_acc, F32, name="P = G f")
+    assert worst > 0.01 and n_acc == 5 + 3
+    with pytest.raises(AssertionError):
+        check_rounded(torch.bmm(got.transpose(1, 2), f), P, pmag, n_acc, F32, name="P = G^T f")
+
+
+def test_propagate_form_mirrors_the_dispatch():
+    want = {(4, 256): "stream4", (28, 256): "stream4", (64, 512): "stream4", (56, 128): "stream2", (20, 384): "stream2",
+            (1, 128): "mfma4", (3, 256): "mfma4", (49, 128): "mfma4", (63, 128): "mfma4", (65, 128): "mfma8", (112, 256): "mfma8",
+            (128, 128): "mfma8", (20, 260): "generic", (130, 128): "generic", (146, 128): "generic", (147, 128): "tiled",
+            (148, 128): "tiled", (149, 128): "tiled", (240, 132): "tiled"}
+    for (V, C), form in want.items():
+        got, n_acc = GR.propagate_form(V, C)
+        assert got == form, (V, C, got)
+        assert n_acc == (-(-V // 4) if form[0] in "sm" else V) + GR.EPILOGUE == GR.form_chain(form, V)
+    # the LDS-resident generic form holds V (Vp + 128) floats, Vp = V rounded up to 8: 146 fits 160 KB, 147 does not
+    assert (146 * (152 + 128)) * 4 <= GR.LDS_BYTES < (147 * (152 + 128)) * 4
+
+
+def _message_fp32(f, h, G, scale, shift, keep, gamma, slope, form, drop_last_row_of=None, slope_on_positive=False):
+    """The message-pass kernels step by step in fp32: one rounding per 4-deep MFMA step (stream, MFMA) or per fma (generic,
+    tiled), then fmaf(acc, scale, shift), the LeakyReLU, keep f + gamma y."""
+    B, V, C = f.shape
+    step = 4 if form[0] in "sm" else 1
+    acc = torch.zeros((B, V, C))
+    Gd = G.double().clone()
+    if drop_last_row_of is not None:
+        b, v = drop_last_row_of
+        Gd[b, v, V - 1] = 0
+    for u0 in range(0, V, step):
+        acc = (acc.double() + torch.bmm(Gd[:, :, u0:u0 + step], h[:, u0:u0 + step].double())).float()
+    y = (acc.double() * scale.double() + shift.double()).float()
+    s = torch.tensor(slope, dtype=F32)
+    y = torch.where((y <= 0) if slope_on_positive else (y > 0), y, s * y)
+    return torch.tensor(keep, dtype=F32) * f + torch.tensor(gamma, dtype=F32) * y
+
+
+def _double_rounded(v, dtype):
+    """fp32 -> one significand bit more than ``dtype`` keeps -> ``dtype``: a copy rounded twice."""
+    p = 11 if dtype == torch.float16 else 8
+    m, e = torch.frexp(v.double())
+    mid = torch.ldexp(torch.round(m * 2.0 ** (p + 1)) / 2.0 ** (p + 1), e)
+    return mid.float().to(dtype)
+
+
+@pytest.mark.parametrize("dtype", LP_TYPES)
+@pytest.mark.parametrize("cfg", [(2, 28, 256, 0.9, 0.1), (2, 49, 128, 1.0, 0.3), (2, 20, 260, 0.0, 1.0), (1, 149, 128, 1.0, 0.3)])
+def test_message_reference_accepts_each_form_and_rejects_seeded_faults(cfg, dtype):
+    B, V, C, keep, gamma = cfg
+    form, n_acc = GR.propagate_form(V, C)
+    g = torch.Generator().manual_seed(V + C)
+    f, h = torch.randn((B, V, C), generator=g), torch.randn((B, V, C), generator=g) * R.channel_scales(C, 3, -8, 2)
+    G = torch.randn((B, V, V), generator=g) / V ** 0.5
+    scale, shift = torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)
+    slope = 0.1
+    exact, mag, n = GR.message_ref(f, h, G, scale, shift, keep, gamma, slope, form)
+    assert n == n_acc
+    got = _message_fp32(f, h, G, scale, shift, keep, gamma, slope, form)
+    worst, _ = check_rounded(got, exact, mag, n, F32, name="message " + form)
+    assert worst > 0.01, "n_acc is within two orders of what fp32 does"
+    # the last graph row u = V - 1 dropped from one output node
+    bad = _message_fp32(f, h, G, scale, shift, keep, gamma, slope, form, drop_last_row_of=(B - 1, V // 2))
+    with pytest.raises(AssertionError, match=r"at \(%d, %d, \d+\)" % (B - 1, V // 2)):
+        check_rounded(bad, exact, mag, n, F32, name="message, last graph row dropped")
+    # G used transposed
+    with pytest.raises(AssertionError):
+        check_rounded(_message_fp32(f, h, G.transpose(1, 2), scale, shift, keep, gamma, slope, form), exact, mag, n, F32, name="message, G^T")
+    # slope applied to the positive side
+    with pytest.raises(AssertionError):
+        check_rounded(_message_fp32(f, h, G, scale, shift, keep, gamma, slope, form, slope_on_positive=True), exact, mag, n, F32, name="message, slope on the wrong side")
+    # keep taken as fp32 1 - gamma where the host passes another keep (ganet: keep = 1; P = G f: keep = 0)
+    if abs(keep - (1 - gamma)) > 1e-3:
+        wrong = float(torch.tensor(1.0) - torch.tensor(gamma, dtype=F32))
+        with pytest.raises(AssertionError):
+            check_rounded(_message_fp32(f, h, G, scale, shift, wrong, gamma, slope, form), exact, mag, n, F32, name="message, keep = 1 - gamma")
+    else:   # the reference's Python-float 1 - gamma rounded once is what the host passes: the fp32 difference may be an ulp off, inside the bound
+        wrong = float(torch.tensor(1.0) - torch.tensor(gamma, dtype=F32))
+        check_rounded(_message_fp32(f, h, G, scale, shift, wrong, gamma, slope, form), exact, mag, n, F32, name="message, fp32 1 - gamma")
+    # the 16-bit copy: the one rounding of the fp32 output, every element; a copy rounded twice is not
+    zero = torch.zeros_like(exact)
+    check_rounded(got.to(dtype), got.double(), zero, 0, dtype, min_exact_frac=1.0, name="out_lp")
+    check_rounded(got.to(dtype), exact, mag, n, dtype, name="out_lp against float64")
+    with pytest.raises(AssertionError, match="exact-match fraction"):
+        check_rounded(_double_rounded(got, dtype), got.double(), zero, 0, dtype, min_exact_frac=1.0, name="out_lp rounded twice")
+
+
+@pytest.mark.parametrize("mode", GR.LINEAR_MODES)
+@pytest.mark.parametrize("shape", [(84, 64, 128), (129, 192, 256)])
+def test_linear_mix_reference_accepts_each_mode(shape, mode):
+    M, K, N = shape
+    g = torch.Generator().manual_seed(M + K)
+    P, W = torch.randn((1, M, K), generator=g), torch.randn((N, K), generator=g) / K ** 0.5
+    f = torch.randn((1, M, N), generator=g)
+    scale, shift = torch.randn(N, generator=g), 0.3 * torch.randn(N, generator=g)
+    if mode == "lp16":
+        P, W = P.half().float(), W.half().float()
+    exact, mag, n_acc, slack = GR.linear_mix_ref(P, W, f, scale, shift, 1.0, 0.3, 0.1, mode)
+    assert n_acc == n_acc_for(K, 16 if mode == "lp16" else 4) + 4
+
+    def emulate(k_end=K, slope_on_positive=False):
+        if mode == "bf16x3":
+            acc = R.split_product(P[0, :, None, :k_end], W[None, :, :k_end]).sum(2).float()
+        elif mode == "fp16x3":
+            ph, wh = P[0].half(), W.half()
+            pl, wl = (P[0] - ph.float()).half(), (W - wh.float()).half()
+            acc = (ph.double()[:, :k_end] @ wh.double()[:, :k_end].t() + pl.double()[:, :k_end] @ wh.double()[:, :k_end].t()
+                   + ph.double()[:, :k_end] @ wl.double()[:, :k_end].t()).float()
+        else:
+            acc = P[0, :, :k_end] @ W[:, :k_end].t()
+        y = (acc.double() * scale.double() + shift.double()).float()
+        y = torch.where((y <= 0) if slope_on_positive else (y > 0), y, torch.tensor(0.1) * y)
+        return torch.tensor(1.0) * f[0] + torch.tensor(0.3) * y
+    worst, _ = check_rounded(emulate(), exact, mag, n_acc, F32, slack=slack, name="linear mix " + mode)
+    assert worst > 0.01 or mode == "fp16x3"      # (fp16 halves keep 22 bits: far inside the shared split constant)
+    for fault in ({"k_end": K - 32}, {"slope_on_positive": True}):       # the last half k-tile never multiplied; slope on the wrong side
+        with pytest.raises(AssertionError):
+            check_rounded(emulate(**fault), exact, mag, n_acc, F32, slack=slack, name="linear mix, fault")
+    rows = torch.tensor([0, M - 1])
+    e2, m2, _, s2 = GR.linear_mix_ref(P, W, f, scale, shift, 1.0, 0.3, 0.1, mode, rows=rows)
+    tiny = 1e-12 * float(mag.max())          # the same sums on a row subset (float64 BLAS: another blocking)
+    assert float((e2 - exact[rows]).abs().max()) <= tiny and float((m2 - mag[rows]).abs().max()) <= tiny and float((s2 - slack[rows]).abs().max()) <= tiny
+
+
+def _attn_pool_fp32(nodes, sqn, gsum, gs, gsh, as_, ash, hw, over_parts=None):
+    """attn_pool_bnneck_kernel step by step in fp32."""
+    B, S, P, C = nodes.shape
+    n = torch.sqrt(sqn).view(B, S, P)
+    tot = torch.zeros((B, P))
+    for s in range(S):
+        tot = tot + n[:, s]
+    a = n / tot.clamp(min=1e-12)[:, None, :]
+    if over_parts is not None:
+        b_, s_, p_ = over_parts
+        a[b_, s_, p_] = n[b_, s_, p_] / n[b_, s_].sum().clamp(min=1e-12)
+    att = torch.zeros((B, C))
+    for p in range(P):
+        fuse = torch.zeros((B, C))
+        for s in range(S):
+            fuse = (a[:, s, p, None].double() * nodes[:, s, p].double() + fuse.double()).float()
+        att = att + fuse
+    att = att / torch.tensor(float(P))
+    gg = torch.zeros((B, C))
+    for s in range(S):
+        gg = gg + gsum.view(B, S, C)[:, s]
+    gg = gg * (torch.tensor(1.0) / (torch.tensor(float(S)) * torch.tensor(float(hw))))
+    out = torch.cat([(gg.double() * gs.double() + gsh.double()).float(), (att.double() * as_.double() + ash.double()).float()], 1)
+    return out, gg, att
+
+
+@pytest.mark.parametrize("cfg", [(3, 8, 7, 256, 128), (2, 3, 5, 260, 60), (1, 9, 1, 4, 1)])
+def test_attention_pool_reference_accepts_the_fp32_formulas(cfg):
+    B, S, P, C, hw = cfg
+    g = torch.Generator().manual_seed(S * P + C)
+    nodes = torch.rand((B, S, P, C), generator=g) * R.channel_scales(C, 2, -10, 2)
+    nodes[B - 1, min(2, S - 1)] = 0          # a frame whose nodes are all zero
+    if P > 1:
+        nodes[0, :, P - 1] = 0               # a part that is zero in every frame: the denominator sits at the clamp
+    gsum = torch.rand((B * S, C), generator=g) * hw * R.channel_scales(C, 4, -10, 2)
+    one, zero_ = torch.ones(C), torch.zeros(C)
+    sqn = (nodes * nodes).sum(3).reshape(-1)
+    ref = GR.attn_pool_ref(nodes, sqn, gsum, one, zero_, one, zero_, hw)
+    out, gf, af = _attn_pool_fp32(nodes, sqn, gsum, one, zero_, one, zero_, hw)
+    worst = [check_rounded(t, *ref[k], F32, name="attn pool " + k)[0] for k, t in (("out", out), ("g_f", gf), ("att_f", af))]
+    assert min(worst) > 0.01, worst
+    if P > 1:
+        assert float(ref["att_f"][0][0].abs().max()) > 0 and bool(torch.isfinite(out).all())
+        s_ = 0 if S == 1 else 1
+        _, _, bad = _attn_pool_fp32(nodes, sqn, gsum, one, zero_, one, zero_, hw, over_parts=(0, s_, 0))
+        with pytest.raises(AssertionError, match=r"at \(0, \d+\)"):
+            check_rounded(bad, *ref["att_f"], F32, name="attention weight normalised over the parts")
+        # ... and the same fault in the reference is what that output matches
+        check_rounded(bad, *GR.attn_pool_ref(nodes, sqn, gsum, one, zero_, one, zero_, hw, normalise_over_parts=(0, s_, 0))["att_f"], F32, name="the fault against itself")
+    # a real BatchNorm pair in the epilogue
+    sc, sh = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    ref = GR.attn_pool_ref(nodes, sqn, gsum, sc, sh, -sc, sh, hw)
+    out, _, _ = _attn_pool_fp32(nodes, sqn, gsum, sc, sh, -sc, sh, hw)
+    check_rounded(out, *ref["out"], F32, name="attn pool, BatchNorm")
+
+
+@pytest.mark.parametrize("cfg", [(3, 1, 40), (2, 11, 64), (7, 3, 10)])
+def test_clip_mean_reference(cfg):
+    T, n, D = cfg
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn((T * n, D), generator=g) * R.channel_scales(D, 6)
+    acc = x.view(T, n, D)[:, 0].clone()
+    for i in range(1, n):
+        acc = acc + x.view(T, n, D)[:, i]
+    got = acc / torch.tensor(float(n))
+    exact, mag, n_acc = GR.clip_mean_ref(x, n)
+    worst, _ = check_rounded(got, exact, mag, n_acc, F32, name="clip mean")
+    assert n_acc == n + 1 and (worst > 0.01 or n == 1)
+    if n > 1:
+        with pytest.raises(AssertionError):
+            check_rounded(acc / torch.tensor(float(n - 1)), exact, mag, n_acc, F32, name="mean divided by n - 1")
+        check_rounded(acc / torch.tensor(float(n - 1)), *GR.clip_mean_ref(x, n, denominator=n - 1), F32, name="the fault against itself")
+
+
+@pytest.mark.parametrize("dtype", LP_TYPES)
+def test_pam_pool_reference_on_a_16_bit_map(dtype):
+    from torchreid import hip_ops as ops
+    Fr, h, w, C, Cq, splits = 2, 6, 4, 16, 4, [4]      # a short energy chain (Cq = 4): the worst-case bound grows with Cq, fp32's error with its root
+    g = torch.Generator().manual_seed(6)
+    x = (0.5 * torch.randn((Fr, h, w, C), generator=g)).to(dtype).float()
+    qk = x[..., :2 * Cq].contiguous()
+    ref = GR.pam_pool_ref(x, qk, splits, ops.pam_nodes_backward_reference)
+    P = sum(splits)
+    xbar, xmean = torch.zeros((Fr, P, C)), torch.zeros((Fr, P, C))
+    for part, (r0, r1) in enumerate(ops.pam_slices(splits, h)):
+        L = (r1 - r0) * w
+        X = x[:, r0:r1].reshape(Fr, L, C)
+        A = torch.softmax(X[..., :Cq] @ X[..., Cq:2 * Cq].transpose(1, 2), dim=2)
+        abar = A.sum(1) / L
+        xbar[:, part] = torch.einsum('fq,fqc->fc', abar, X)
+        xmean[:, part] = X.sum(1) / L
+    e, m, n, s = ref["xbar"]
+    worst, _ = check_rounded(xbar, e, m, n, F32, slack=s, name="pam xbar")
+    assert worst > 0.01
+    check_rounded(xmean, *ref["xmean"], F32, name="pam xmean")
+    assert float(ref["xbar"][2][0, 0, 0]) == 4 and h // 4 == 1          # h = 6, n = 4: one row per slice, two rows dropped
+    bad = xbar.clone()
+    bad[1, 2] = torch.einsum('fqc->fc', x[1:2, 2:3].reshape(1, w, C)) / w      # the plain mean where the attention-weighted one belongs
+    with pytest.raises(AssertionError, match=r"at \(1, 2, "):
+        check_rounded(bad, e, m, n, F32, slack=s, name="pam xbar, attention dropped")

@@ -3,7 +3,7 @@ under the same parity tests as the default fp16 library, inside the default ``-m
 
 The 16-bit type is fixed when torchreid is imported (AGRL_HIP_LP16), so the bf16 build runs in a FRESH CHILD interpreter -- started
 with subprocess, never a re-exec of a process that has touched the GPU -- on: the B = 32, S = 8 stage-by-stage test (the benchmarked
-dispatch), every 16-bit kernel case of tests/test_gpu_kernels.py, the model-level 16-bit tests and the whole-pipeline Rank-1 / mAP
+dispatch), every 16-bit kernel case of tests/test_gpu_kernels.py, the elementwise bounds of tests/test_gpu_graph_bounds.py, the model-level 16-bit tests and the whole-pipeline Rank-1 / mAP
 test. The tests read their bars from tests/lp16.py (bf16: 8 significand bits -- 1e-2 per stage / 5e-2 on the embedding; fp16 is held
 to the north star's 1e-3)."""
 import os
@@ -27,7 +27,7 @@ def test_bf16_build_passes_the_16_bit_parity_tests_in_a_fresh_process():
            "tests/test_gpu_model.py::test_vmgn_eval_16_bit_mode_close_and_ranking_preserved",
            "tests/test_gpu_model.py::test_vmgn_eval_shape_variants",
            "tests/test_gpu_eval.py::test_16_bit_pipeline_keeps_rank1_and_map",
-           "tests/test_gpu_kernels.py"]
+           "tests/test_gpu_kernels.py", "tests/test_gpu_graph_bounds.py"]
     out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + sel, env=env, cwd=ROOT,
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=3000)
     tail = out.stdout.decode()[-3000:]

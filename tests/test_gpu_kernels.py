@@ -1409,11 +1409,13 @@ def test_attention_tail():
     assert rel_err(out, ref) < 1e-5 and rel_err(gf, g_f) < 1e-5 and rel_err(af, att_f) < 1e-5
 
 
-@pytest.mark.parametrize("cfg", [(32, 8, 7, 2048, 128), (3, 8, 7, 2048, 128), (2, 16, 7, 2048, 128), (5, 4, 3, 512, 60), (1, 1, 7, 256, 128)])
+@pytest.mark.parametrize("cfg", [(32, 8, 7, 2048, 128), (3, 8, 7, 2048, 128), (2, 16, 7, 2048, 128), (5, 4, 3, 512, 60), (1, 1, 7, 256, 128),
+                                 (2, 3, 5, 260, 60), (1, 9, 1, 4, 1)])
 def test_attention_tail_one_launch(cfg):
     """agrl_attn_tail = agrl_row_sqnorm (node norms) + agrl_attn_pool_bnneck + the distance matrix's query operand (agrl_row_sqnorm and
     agrl_row_l2_normalize over the embedding rows, both operand types) in ONE launch: every output BIT-IDENTICAL to the separate
-    launches (each sum runs in the order of the kernel it replaces) -- bench shape, a zero frame, seq_len 16, small widths, one frame."""
+    launches (each sum runs in the order of the kernel it replaces) -- bench shape, a zero frame, seq_len 16, small widths, one frame,
+    widths that end inside the last 256-channel block (260, 4), one part."""
     from torchreid import hip_ops as ops
     B, S, P, C, hw = cfg
     g = torch.Generator().manual_seed(B * 7 + S)

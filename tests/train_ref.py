@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import graph_ref
 from bounds import U32
 
 # ---- split-bf16 products (igemm_dev.h, Frag<f32s_t>) -------------------------------------------------------------------------
@@ -531,29 +532,13 @@ def graph_matrix_backward_ref(gram_part, dG, use_pose, mask_diag=False):
       dS: (dc + u (|dShat| + |c|)) / r + |dS| (dr / r + u);  dD: |dS| (|1 - S| dS_err + 3 u h) + h ddS + u |dD|, h = S (1 - S / 2);
       E: ddD / (2 D) + |E| (dD_err / D + 2 u);  T: dE_ij + dE_ji + u |T|;  rowsum: sum_j dT_ij + t u sum_j |T_ij|;
       M: 2 (drowsum [i = j] + dT) + u |M|.
-    The D2 step is the ill-conditioned one (similar nodes: D2 << g_ii + g_jj); the bound carries that conditioning."""
+    The D2 step is the ill-conditioned one (similar nodes: D2 << g_ii + g_jj); the bound carries that conditioning. The stages up
+    to Shat are graph_ref.similarity_chain (shared with the forward reference graph_ref.graph_matrix_ref)."""
     u = U32
-    gp = gram_part.double()
-    B, nz, V, _ = gp.shape
-    g, a = gp.sum(1), nz * u * gp.abs().sum(1)
-    n, an = torch.diagonal(g, dim1=1, dim2=2), torch.diagonal(a, dim1=1, dim2=2)
-    eye = torch.eye(V, dtype=torch.bool).view(1, V, V)
-    D2 = n[:, :, None] + n[:, None, :] - 2 * g
-    eD2 = an[:, :, None] + an[:, None, :] + 2 * a + 2 * u * (n[:, :, None] + n[:, None, :] + 2 * g.abs())
-    eD2 = eD2.masked_fill(eye, 0.0)        # (g_ii + g_ii) - 2 g_ii is exactly 0 in fp32 too: the diagonal sits at the clamp in both
-    live = (D2 > 1e-12) & ~eye
-    D = D2.clamp(min=1e-12).sqrt()
-    eD = eD2 / (2 * D) + u * D
-    S = 2 / (torch.exp(D) + 1)
-    h = S * (1 - S / 2)
-    eS = h * eD + 4 * u * S
-    if mask_diag:
-        S, h, eS = S.masked_fill(eye, 0.0), h.masked_fill(eye, 0.0), eS.masked_fill(eye, 0.0)
+    V = gram_part.shape[-1]
+    ch = graph_ref.similarity_chain(*graph_ref.gram_from_partials(gram_part), mask_diag=mask_diag)   # up to Shat: one copy, shared with the forward reference
+    D, eD, S, h, eS, r, er, Sh, eSh, live = (ch[k] for k in ("D", "eD", "S", "h", "eS", "r", "er", "Sh", "eSh", "live"))
     t = -(-V // 64) + 6
-    r = S.sum(2, keepdim=True)
-    er = eS.sum(2, keepdim=True) + t * u * r
-    Sh = S / r
-    eSh = Sh * (eS / S.clamp(min=1e-300) + er / r + u)
     x = dG.double() * (0.5 if use_pose else 1.0)
     c = (x * Sh).sum(2, keepdim=True)
     ec = (x.abs() * eSh).sum(2, keepdim=True) + t * u * (x * Sh).abs().sum(2, keepdim=True)
