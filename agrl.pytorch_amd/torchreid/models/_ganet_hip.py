@@ -1,5 +1,5 @@
 """MI355X execution of the sibling model ``ganet``'s eval forward (reference torchreid/models/ganet.py:378-424) through the
-C-ABI of libagrl_hip.so. Same conv kernels and data layout as vmgn (``_vmgn_hip``); what is specific:
+C-ABI of libagrl_hip.so. Same conv kernels, data layout and host path as vmgn (``_resnet_hip``); what is specific:
 
     part nodes   ganet.py:384-400: every pyramid slice through the position attention module, ``pam(slice) + slice``
                  average pooled. The value conv (2048 -> 2048 on every position, three pyramid levels) is never evaluated per
@@ -19,62 +19,40 @@ import torch
 
 from torchreid import hip_ops as ops
 from torchreid import _hip
-from torchreid.models._vmgn_hip import (_PRECISIONS, eval_frames, run_stem, _fingerprint, _fold_bn1d, _fold_conv_bn, _pack_stage, _run_block, _run_trunk,
-                                         check_packed_range)
+import torchreid.models._resnet_hip as R
+
+
+def _pack_entries(model, pack, dtype, s16):
+    """The position attention module, the BNNeck and the graph layers. ('fp16x3': the conv trunk in the split-fp16 arithmetic as in
+    vmgn / gsta; the attention module, the graph layers and the tail stay exact fp32)"""
+    pam = model.pam_layer
+    pack.update({
+        # stacked query / key conv as one OHWI weight (2*Cq, 1, 1, C) + bias; value conv as a Linear weight (C, C) + bias
+        'qk_w': torch.cat([pam.query_conv.weight, pam.key_conv.weight], 0).detach().float().permute(0, 2, 3, 1).contiguous().to(dtype),
+        'qk_b': torch.cat([pam.query_conv.bias, pam.key_conv.bias], 0).detach().float().contiguous(),
+        'cq': pam.query_conv.weight.shape[0],
+        'v_w': pam.value_conv.weight.detach().float().view(pam.value_conv.weight.shape[0], -1).contiguous().to(dtype),
+        'v_b': pam.value_conv.bias.detach().float().contiguous(),
+        'pam_gamma': float(pam.gamma.detach()),
+        'bnneck': R.single_bnneck(model.bottleneck),
+        'graph': [],
+    })
+    for layer in model.graph_layers:
+        scale, shift = R.fold_bn1d(layer.bn)
+        pack['graph'].append({'w': layer.linear.weight.detach().to(dtype).contiguous(), 'scale': scale, 'shift': shift,
+                              'slope': float(layer.relu.negative_slope), 'use_pose': bool(layer.use_pose),
+                              'learn_graph': bool(layer.learn_graph)})
 
 
 def pack_weights(model, device, precision):
-    ops.check_precision(precision)
-    key = (device.index if device.index is not None else torch.cuda.current_device(), precision)
-    cached = model._hip_packs.get(key)
-    if cached is not None and (model.hip_static_weights or cached['fingerprint'] == _fingerprint(model)):
-        return cached
-    first = next(model.parameters())
-    if first.device != device:
-        raise RuntimeError('model parameters live on {} but the input is on {}'.format(first.device, device))
-    dtype = _PRECISIONS[precision]
-    s16 = precision == 'fp16x3'
-    pam = model.pam_layer
-    with torch.no_grad():
-        stem_w, stem_b = _fold_conv_bn(model.conv1, model.bn1, torch.float32)
-        cq = pam.query_conv.weight.shape[0]
-        pack = {
-            'dtype': dtype,
-            'stem': (stem_w, stem_b),
-            'stem_lp': ops.pack_stem_weights_lp16(stem_w) if dtype == ops.LP_DTYPE else None,
-            'stem_s16': ops.pack_stem_weights_split16(stem_w) if s16 else None,
-            # ('fp16x3': the conv trunk in the split-fp16 arithmetic -- pre-scaled weights, agrl_conv2d_bn_act_split16 -- as in vmgn / gsta;
-            # the attention module, the graph layers and the tail stay exact fp32)
-            'trunk': (_pack_stage(model.layer1, dtype, split16=s16) + _pack_stage(model.layer2, dtype, split16=s16)
-                      + _pack_stage(model.layer3, dtype, seam=True, split16=s16)),
-            'l4': _pack_stage(model.layer4, dtype, split16=s16),
-            # stacked query / key conv as one OHWI weight (2*Cq, 1, 1, C) + bias; value conv as a Linear weight (C, C) + bias
-            'qk_w': torch.cat([pam.query_conv.weight, pam.key_conv.weight], 0).detach().float().permute(0, 2, 3, 1).contiguous().to(dtype),
-            'qk_b': torch.cat([pam.query_conv.bias, pam.key_conv.bias], 0).detach().float().contiguous(),
-            'cq': cq,
-            'v_w': pam.value_conv.weight.detach().float().view(pam.value_conv.weight.shape[0], -1).contiguous().to(dtype),
-            'v_b': pam.value_conv.bias.detach().float().contiguous(),
-            'pam_gamma': float(pam.gamma.detach()),
-            'bn': _fold_bn1d(model.bottleneck),
-            'graph': [],
-        }
-        for layer in model.graph_layers:
-            scale, shift = _fold_bn1d(layer.bn)
-            pack['graph'].append({'w': layer.linear.weight.detach().to(dtype).contiguous(), 'scale': scale, 'shift': shift,
-                                  'slope': float(layer.relu.negative_slope), 'use_pose': bool(layer.use_pose),
-                                  'learn_graph': bool(layer.learn_graph)})
-    if dtype == ops.LP_DTYPE:
-        check_packed_range(pack, 'ganet')
-    pack['fingerprint'] = _fingerprint(model)
-    model._hip_packs[key] = pack
-    return pack
+    return R.pack_weights(model, device, precision, _pack_entries, 'ganet')
 
 
 def hip_forward_ganet(model, x, adj, stages=None):
     """Eval forward of ``ganet`` on the GPU: (B,S,3,H,W) fp32 (or uint8 frames, see _vmgn_hip.hip_forward), (B,V,V) fp32 ->
     (B, (num_gb + 1) * 2048) fp32."""
     _hip.lib()
-    frames, B, S, norm = eval_frames(model, x)
+    frames, B, S, norm = R.eval_frames(model, x)
     P = model.total_split
     V = S * P
     if tuple(adj.shape) != (B, V, V):
@@ -83,10 +61,7 @@ def hip_forward_ganet(model, x, adj, stages=None):
     lp = pack['dtype'] == ops.LP_DTYPE
     splits = list(model.total_split_list)
     with torch.no_grad(), ops.f32_split(model.hip_precision == 'bf16x3'):
-        a = run_stem(frames, pack, norm)
-        a = _run_trunk(a, pack['trunk'])
-        for blk in pack['l4']:
-            a = _run_block(a, blk)
+        a = R.run_layer4(R.run_trunk(R.run_stem(frames, pack, norm), pack['trunk']), pack['l4'])
         C = a.shape[-1]
         # ---- position-attention part nodes
         gamma_p = pack['pam_gamma']
@@ -120,12 +95,7 @@ def hip_forward_ganet(model, x, adj, stages=None):
             nxt, nodes_lp = ops.graph_propagate(cur, h, G, g['scale'], g['shift'], gamma_g, g['slope'], want_lp=lp, keep=1.0)
             outs.append(nxt)
         cat = torch.cat(outs, dim=2).contiguous()
-        Ct = cat.shape[-1]
         if stages is not None:
             stages.update(nodes=nodes, cat=cat)
         # ---- attention pooling + BNNeck over the concatenated channels
-        sqn = ops.row_sqnorm(cat.view(B * V, Ct))
-        gsum = torch.zeros((B * S, Ct), dtype=torch.float32, device=x.device)
-        ident = (torch.ones_like(pack['bn'][0]), torch.zeros_like(pack['bn'][1]))
-        out = ops.attn_pool_bnneck(cat, sqn, gsum, ident[0], ident[1], pack['bn'][0], pack['bn'][1], B, S, P, 1)
-        return out[:, Ct:].contiguous()
+        return R.single_branch_tail(cat, pack['bnneck'], B, S, P, 1)

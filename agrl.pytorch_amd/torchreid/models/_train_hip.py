@@ -19,6 +19,7 @@ Layout: NHWC fp32 between the nodes (the layout of the eval path); NCHW only at 
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from torchreid import hip_ops as ops
@@ -305,25 +306,31 @@ def featuremaps_train(model, frames_nchw):
     """GSTA.featuremaps (vmgn.py:280-290) under model.train() on the GPU -> x4_1, x4_2 as NCHW views for the tail.
     ``model.hip_train_precision``: 'fp32' = exact-fp32 MFMA (bitwise an fp32 fma chain, the parity mode); 'bf16x3' = fp32 tensors,
     every GEMM product as three bf16 MFMAs on the high / low halves of the operands (~1e-5 relative, 1.6 x the rate)."""
+    with train_precision(model):
+        return [b.permute(0, 3, 1, 2) for b in trunk_train(model, frames_nchw)]
+
+
+def train_precision(model):
+    """``model.hip_train_precision`` validated -> the context of its GEMM arithmetic (ops.f32_split) for the native step."""
     prec = getattr(model, 'hip_train_precision', 'fp32')
     if prec not in ('fp32', 'bf16x3'):
         raise ValueError("hip_train_precision must be 'fp32' or 'bf16x3', got {!r}".format(prec))
-    with ops.f32_split(prec == 'bf16x3'):
-        return _featuremaps_train(model, frames_nchw)
+    return ops.f32_split(prec == 'bf16x3')
 
 
-def _featuremaps_train(model, frames_nchw):
+def trunk_train(model, frames_nchw):
+    """The stem, layers 1-3 and the layer-4 stage(s) under model.train() -> [map] or, for vmgn's two branches, [x4_1, x4_2], NHWC."""
     a = stem_train(model, frames_nchw)
     for stage in (model.layer1, model.layer2, model.layer3):
         for unit in stage:
             a = bottleneck_train(unit, a)
-    outs = []
-    for stage in ([model.layer4_1, model.layer4_2] if hasattr(model, 'layer4_1') else [model.layer4]):
+    maps = []
+    for stage in ((model.layer4_1, model.layer4_2) if hasattr(model, 'layer4_1') else (model.layer4,)):
         b = a
         for unit in stage:
             b = bottleneck_train(unit, b)
-        outs.append(b.permute(0, 3, 1, 2))
-    return outs
+        maps.append(b)
+    return maps
 
 
 # =====================================================================================================================
@@ -556,37 +563,53 @@ def tail_train(model, x4_1, x4_2, adj, B, S):
 def forward_train(model, x, adj):
     """GSTA.forward under model.train() on the GPU, every arithmetic step a C-ABI call."""
     B, S, C, H, W = x.shape
-    prec = getattr(model, 'hip_train_precision', 'fp32')
-    if prec not in ('fp32', 'bf16x3'):
-        raise ValueError("hip_train_precision must be 'fp32' or 'bf16x3', got {!r}".format(prec))
-    with ops.f32_split(prec == 'bf16x3'):
-        a = stem_train(model, x.view(B * S, C, H, W))
-        for stage in (model.layer1, model.layer2, model.layer3):
-            for unit in stage:
-                a = bottleneck_train(unit, a)
-        maps = []
-        for stage in (model.layer4_1, model.layer4_2):
-            b = a
-            for unit in stage:
-                b = bottleneck_train(unit, b)
-            maps.append(b)
-        return tail_train(model, maps[0], maps[1], adj, B, S)
+    with train_precision(model):
+        x4_1, x4_2 = trunk_train(model, x.view(B * S, C, H, W))
+        return tail_train(model, x4_1, x4_2, adj, B, S)
+
+
+def drop_one_frame(B, S, device):
+    """The consistent loss of gsta and ganet: per tracklet the S - 1 frames left when one random frame is dropped -> (B, S - 1) int64
+    on ``device``. Drawn from numpy's global RNG like the reference (gsta.py:300-311): B calls of np.random.randint(S), in order."""
+    keep = []
+    for _ in range(B):
+        idx = list(range(S))
+        idx.remove(np.random.randint(S))
+        keep.append(idx)
+    return torch.LongTensor(keep).to(device)
+
+
+def loss_outputs(model, y, sy, f_g, sf_g):
+    """What gsta's and ganet's forward return under train(), by ``model.loss`` (gsta.py:313-322)."""
+    if model.loss == {'xent'}:
+        return [y, sy] if model.consistent_loss else y
+    if model.loss == {'xent', 'htri'}:
+        return ([y, sy], [f_g, sf_g]) if model.consistent_loss else (y, f_g)
+    raise KeyError('Unsupported loss: {}'.format(model.loss))
+
+
+def _single_branch_head(model, f):
+    """Attention pooling, BNNeck and classifier of gsta / ganet on the nodes f (B,S,P,C), with the one-frame-dropped consistent loss."""
+    B, S, P, C = f.shape
+    f_g = HipAttnPool.apply(f)
+    bn = _bn_act(model.bottleneck, f_g, None, False)
+    sy = sf_g = None
+    if model.consistent_loss:
+        keep = drop_one_frame(B, S, f.device)
+        sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, P, C))
+        sf_g = HipAttnPool.apply(sf)
+        sy = linear_train(_bn_act(model.bottleneck, sf_g, None, False), model.classifier.weight)
+    y = linear_train(bn, model.classifier.weight)
+    return loss_outputs(model, y, sy, f_g, sf_g)
 
 
 def forward_train_gsta(model, x, adj):
     """The single-branch sibling ``gsta`` under model.train() on the GPU (reference gsta.py:273-322): the same native nodes as
     vmgn's step -- conv trunk with batch-statistics BatchNorm, part pooling, graph layers, attention pooling, BNNeck, classifier --
     and its consistent loss (one random frame dropped per tracklet, drawn from numpy's global RNG like the reference)."""
-    import numpy as np
     B, S, C, H, W = x.shape
-    prec = getattr(model, 'hip_train_precision', 'fp32')
-    if prec not in ('fp32', 'bf16x3'):
-        raise ValueError("hip_train_precision must be 'fp32' or 'bf16x3', got {!r}".format(prec))
-    with ops.f32_split(prec == 'bf16x3'):
-        a = stem_train(model, x.view(B * S, C, H, W))
-        for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
-            for unit in stage:
-                a = bottleneck_train(unit, a)
+    with train_precision(model):
+        a, = trunk_train(model, x.view(B * S, C, H, W))
         P = model.total_split
         # the part nodes only (gsta has no global branch): the pooling node takes the map for both of its inputs, the unused
         # global feature contributes a zero gradient
@@ -596,26 +619,7 @@ def forward_train_gsta(model, x, adj):
         adj = adj.detach().to(torch.float32).contiguous()
         for layer in model.graph_layers:
             f = graph_layer_train(layer, f, adj)
-        f = f.view(B, S, P, Cf)
-        f_g = HipAttnPool.apply(f)
-        bn = _bn_act(model.bottleneck, f_g, None, False)
-        sy = sf_g = None
-        if model.consistent_loss:
-            keep = []
-            for _ in range(B):
-                idx = list(range(S))
-                idx.remove(np.random.randint(S))
-                keep.append(idx)
-            keep = torch.LongTensor(keep).to(f.device)
-            sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, P, Cf))
-            sf_g = HipAttnPool.apply(sf)
-            sy = linear_train(_bn_act(model.bottleneck, sf_g, None, False), model.classifier.weight)
-        y = linear_train(bn, model.classifier.weight)
-    if model.loss == {'xent'}:
-        return [y, sy] if model.consistent_loss else y
-    if model.loss == {'xent', 'htri'}:
-        return ([y, sy], [f_g, sf_g]) if model.consistent_loss else (y, f_g)
-    raise KeyError('Unsupported loss: {}'.format(model.loss))
+        return _single_branch_head(model, f.view(B, S, P, Cf))
 
 
 def forward_train_ganet(model, x, adj):
@@ -624,16 +628,9 @@ def forward_train_ganet(model, x, adj):
     masked and the residual form ``input + gamma * h'`` (with the constructor's gamma = 0 the message adds nothing, but its
     BatchNorm1d still sees the batch and moves its running statistics, as in the reference), the layers' outputs concatenated
     along the channels in front of the attention pooling, one BNNeck -- and the same one-frame-dropped consistent loss."""
-    import numpy as np
     B, S, C, H, W = x.shape
-    prec = getattr(model, 'hip_train_precision', 'fp32')
-    if prec not in ('fp32', 'bf16x3'):
-        raise ValueError("hip_train_precision must be 'fp32' or 'bf16x3', got {!r}".format(prec))
-    with ops.f32_split(prec == 'bf16x3'):
-        a = stem_train(model, x.view(B * S, C, H, W))
-        for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
-            for unit in stage:
-                a = bottleneck_train(unit, a)
+    with train_precision(model):
+        a, = trunk_train(model, x.view(B * S, C, H, W))
         P = model.total_split
         nodes = pam_nodes_train(model.pam_layer, a, model.total_split_list)
         Cf = nodes.shape[-1]
@@ -641,24 +638,4 @@ def forward_train_ganet(model, x, adj):
         outs = [nodes.view(B, S * P, Cf)]
         for layer in model.graph_layers:
             outs.append(graph_layer_train(layer, outs[-1], adj, mask_diag=True, keep=1.0))
-        Ct = Cf * len(outs)
-        f = torch.cat(outs, dim=2).view(B, S, P, Ct)
-        f_g = HipAttnPool.apply(f)
-        bn = _bn_act(model.bottleneck, f_g, None, False)
-        sy = sf_g = None
-        if model.consistent_loss:
-            keep = []
-            for _ in range(B):
-                idx = list(range(S))
-                idx.remove(np.random.randint(S))
-                keep.append(idx)
-            keep = torch.LongTensor(keep).to(f.device)
-            sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, P, Ct))
-            sf_g = HipAttnPool.apply(sf)
-            sy = linear_train(_bn_act(model.bottleneck, sf_g, None, False), model.classifier.weight)
-        y = linear_train(bn, model.classifier.weight)
-    if model.loss == {'xent'}:
-        return [y, sy] if model.consistent_loss else y
-    if model.loss == {'xent', 'htri'}:
-        return ([y, sy], [f_g, sf_g]) if model.consistent_loss else (y, f_g)
-    raise KeyError('Unsupported loss: {}'.format(model.loss))
+        return _single_branch_head(model, torch.cat(outs, dim=2).view(B, S, P, Cf * len(outs)))

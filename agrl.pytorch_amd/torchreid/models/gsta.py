@@ -14,13 +14,14 @@ __all__ = ['gsta']
 
 import os
 
-import numpy as np
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 from torchreid.utils.reidtools import calc_splits
-from .vmgn import Bottleneck, GraphLayer, RESNET50_STAGES, _make_stage
+from ._resnet_hip import init_hip_attributes
+from ._train_hip import drop_one_frame, loss_outputs
+from .vmgn import Bottleneck, GraphLayer, RESNET50_STAGES, make_stage
 
 
 class GSTASingle(nn.Module):
@@ -37,10 +38,10 @@ class GSTASingle(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         ch = 64
-        self.layer1, ch = _make_stage(ch, 64, layers[0], 1)
-        self.layer2, ch = _make_stage(ch, 128, layers[1], 2)
-        self.layer3, ch = _make_stage(ch, 256, layers[2], 2)
-        self.layer4, ch = _make_stage(ch, 512, layers[3], 1)
+        self.layer1, ch = make_stage(ch, 64, layers[0], 1)
+        self.layer2, ch = make_stage(ch, 128, layers[1], 2)
+        self.layer3, ch = make_stage(ch, 256, layers[2], 2)
+        self.layer4, ch = make_stage(ch, 512, layers[3], 1)
 
         self.num_split = num_split
         self.total_split_list = calc_splits(num_split) if pyramid_part else [num_split]
@@ -56,18 +57,7 @@ class GSTASingle(nn.Module):
         self.classifier = nn.Linear(self.feature_dim, num_classes, bias=False)
         self._init_params()
 
-        # MI355X path configuration (not part of the state dict)
-        self.hip_precision = os.environ.get('AGRL_HIP_PRECISION', 'fp32')
-        from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
-        _ops.check_precision(self.hip_precision)
-        self.hip_static_weights = False
-        self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode forward + backward on the HIP kernels
-        self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')
-        self._hip_packs = {}
-        # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
-        # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
-        self.pixel_mean = (0.485, 0.456, 0.406)
-        self.pixel_std = (0.229, 0.224, 0.225)
+        init_hip_attributes(self, train=True)   # MI355X path configuration (plain attributes, not part of the state dict)
 
     def _init_params(self):
         """reference gsta.py:240-256"""
@@ -111,25 +101,16 @@ class GSTASingle(nn.Module):
         f = f.view(B, S, self.total_split, c)
         f_g = self._attention_op(f).mean(dim=1).view(B, -1)
         bn = self.bottleneck(f_g)
+        sy = sf_g = None
         if self.consistent_loss and self.training:
             # one random frame dropped per tracklet, drawn from numpy's global RNG (reference gsta.py:300-311)
-            keep = []
-            for _ in range(B):
-                idx = list(range(S))
-                idx.remove(np.random.randint(S))
-                keep.append(idx)
-            keep = torch.LongTensor(keep).to(f.device)
+            keep = drop_one_frame(B, S, f.device)
             sf = torch.gather(f, dim=1, index=keep.view(B, S - 1, 1, 1).repeat(1, 1, f.size(2), f.size(3)))
             sf_g = self._attention_op(sf).mean(dim=1).view(B, -1)
             sy = self.classifier(self.bottleneck(sf_g))
         if not self.training:
             return bn
-        y = self.classifier(bn)
-        if self.loss == {'xent'}:
-            return [y, sy] if self.consistent_loss else y
-        elif self.loss == {'xent', 'htri'}:
-            return ([y, sy], [f_g, sf_g]) if self.consistent_loss else (y, f_g)
-        raise KeyError('Unsupported loss: {}'.format(self.loss))
+        return loss_outputs(self, self.classifier(bn), sy, f_g, sf_g)
 
     def invalidate_hip_cache(self):
         self._hip_packs.clear()

@@ -21,7 +21,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .vmgn import Bottleneck, RESNET50_STAGES, _make_stage
+from ._resnet_hip import init_hip_attributes
+from .vmgn import Bottleneck, RESNET50_STAGES, make_stage
 
 
 class ResNet50TP(nn.Module):
@@ -37,10 +38,10 @@ class ResNet50TP(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         ch = 64
-        self.layer1, ch = _make_stage(ch, 64, layers[0], 1)
-        self.layer2, ch = _make_stage(ch, 128, layers[1], 2)
-        self.layer3, ch = _make_stage(ch, 256, layers[2], 2)
-        self.layer4, ch = _make_stage(ch, 512, layers[3], last_stride)   # this one honours last_stride (res50tp.py:129)
+        self.layer1, ch = make_stage(ch, 64, layers[0], 1)
+        self.layer2, ch = make_stage(ch, 128, layers[1], 2)
+        self.layer3, ch = make_stage(ch, 256, layers[2], 2)
+        self.layer4, ch = make_stage(ch, 512, layers[3], last_stride)   # this one honours last_stride (res50tp.py:129)
 
         self.part = 4
         self.avg_pool = nn.AdaptiveAvgPool2d((self.part, 1))
@@ -50,13 +51,7 @@ class ResNet50TP(nn.Module):
         self._init_params()
 
         # MI355X path configuration (not part of the state dict): the plain attributes of GSTASingle
-        self.hip_precision = os.environ.get('AGRL_HIP_PRECISION', 'fp32')
-        from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
-        _ops.check_precision(self.hip_precision)
-        self.hip_static_weights = False
-        self._hip_packs = {}
-        self.pixel_mean = (0.485, 0.456, 0.406)
-        self.pixel_std = (0.229, 0.224, 0.225)
+        init_hip_attributes(self)
 
     def _init_params(self):
         """reference res50tp.py:157-172"""

@@ -18,7 +18,7 @@ __all__ = ['simple_sta']
 from torch import nn
 from torch.nn import functional as F
 
-from .sta import STA, _build
+from .sta import STA, build_sta
 
 
 class SimpleSTA(STA):
@@ -41,4 +41,4 @@ class SimpleSTA(STA):
 def simple_sta(num_classes, loss={'xent', 'htri'}, last_stride=1, pretrained=True, **kwargs):
     """Factory registered as ``'simple_sta'`` (reference simple_sta_p4, simple_sta.py:243-257). Never touches the network:
     ``pretrained`` only takes effect through ``AGRL_PRETRAINED_RESNET50``."""
-    return _build(SimpleSTA, num_classes, loss, last_stride, pretrained, kwargs)
+    return build_sta(SimpleSTA, num_classes, loss, last_stride, pretrained, kwargs)

@@ -22,7 +22,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .vmgn import Bottleneck, RESNET50_STAGES, _make_stage
+from ._resnet_hip import init_hip_attributes
+from .vmgn import Bottleneck, RESNET50_STAGES, make_stage
 
 
 class STA(nn.Module):
@@ -41,10 +42,10 @@ class STA(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         ch = 64
-        self.layer1, ch = _make_stage(ch, 64, layers[0], 1)
-        self.layer2, ch = _make_stage(ch, 128, layers[1], 2)
-        self.layer3, ch = _make_stage(ch, 256, layers[2], 2)
-        self.layer4, ch = _make_stage(ch, 512, layers[3], 1)    # last stride 1 whatever ``last_stride`` says (sta.py:145)
+        self.layer1, ch = make_stage(ch, 64, layers[0], 1)
+        self.layer2, ch = make_stage(ch, 128, layers[1], 2)
+        self.layer3, ch = make_stage(ch, 256, layers[2], 2)
+        self.layer4, ch = make_stage(ch, 512, layers[3], 1)    # last stride 1 whatever ``last_stride`` says (sta.py:145)
 
         self.parts_avgpool = nn.AdaptiveAvgPool2d((self.parts, 1))
         self.dropout = nn.Dropout(p=0.5)                         # never called (sta.py:149)
@@ -54,13 +55,7 @@ class STA(nn.Module):
         self._init_params()
 
         # MI355X path configuration (not part of the state dict): the plain attributes of GSTASingle
-        self.hip_precision = os.environ.get('AGRL_HIP_PRECISION', 'fp32')
-        from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
-        _ops.check_precision(self.hip_precision)
-        self.hip_static_weights = False
-        self._hip_packs = {}
-        self.pixel_mean = (0.485, 0.456, 0.406)
-        self.pixel_std = (0.229, 0.224, 0.225)
+        init_hip_attributes(self)
 
     @staticmethod
     def _head_act(nonlinear):
@@ -123,7 +118,7 @@ class STA(nn.Module):
         self._hip_packs.clear()
 
 
-def _build(cls, num_classes, loss, last_stride, pretrained, kwargs):
+def build_sta(cls, num_classes, loss, last_stride, pretrained, kwargs):
     model = cls(num_classes=num_classes, loss=loss, block=Bottleneck, layers=list(RESNET50_STAGES), last_stride=last_stride,
                 reduced_dim=1024, nonlinear='relu', **kwargs)
     path = os.environ.get('AGRL_PRETRAINED_RESNET50', '')
@@ -138,4 +133,4 @@ def _build(cls, num_classes, loss, last_stride, pretrained, kwargs):
 def sta(num_classes, loss={'xent', 'htri'}, last_stride=1, pretrained=True, **kwargs):
     """Factory registered as ``'sta'`` (reference sta_p4, sta.py:268-282). Never touches the network: ``pretrained`` only takes
     effect through ``AGRL_PRETRAINED_RESNET50`` (a local resnet50-19c8e357.pth)."""
-    return _build(STA, num_classes, loss, last_stride, pretrained, kwargs)
+    return build_sta(STA, num_classes, loss, last_stride, pretrained, kwargs)

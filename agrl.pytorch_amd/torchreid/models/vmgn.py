@@ -30,6 +30,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from torchreid.utils.reidtools import calc_splits
+from ._resnet_hip import init_hip_attributes
 from torchreid.utils.torchtools import weights_init_kaiming, weights_init_classifier
 
 FEATURE_DIM = 2048
@@ -62,7 +63,7 @@ class Bottleneck(nn.Module):
         return self.relu(y)
 
 
-def _make_stage(inplanes, planes, blocks, stride):
+def make_stage(inplanes, planes, blocks, stride):
     """One ResNet stage as nn.Sequential of Bottlenecks; returns (stage, out_channels)."""
     out_ch = planes * Bottleneck.expansion
     downsample = None
@@ -141,10 +142,10 @@ class GSTA(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         ch = 64
-        self.layer1, ch = _make_stage(ch, 64, layers[0], 1)
-        self.layer2, ch = _make_stage(ch, 128, layers[1], 2)
-        self.layer3, ch = _make_stage(ch, 256, layers[2], 2)
-        self.layer4_1, ch = _make_stage(ch, 512, layers[3], 1)
+        self.layer1, ch = make_stage(ch, 64, layers[0], 1)
+        self.layer2, ch = make_stage(ch, 128, layers[1], 2)
+        self.layer3, ch = make_stage(ch, 256, layers[2], 2)
+        self.layer4_1, ch = make_stage(ch, 512, layers[3], 1)
         _load_local_pretrained(self)
         self.layer4_2 = copy.deepcopy(self.layer4_1)
 
@@ -173,19 +174,7 @@ class GSTA(nn.Module):
         weights_init_kaiming(self.att_bottleneck)
         weights_init_classifier(self.att_classifier)
 
-        # MI355X path configuration (not part of the state dict)
-        self.hip_precision = os.environ.get('AGRL_HIP_PRECISION', 'fp32')
-        from torchreid import hip_ops as _ops   # a precision the loaded library cannot serve fails HERE, not at the first forward
-        _ops.check_precision(self.hip_precision)
-        self.hip_static_weights = False
-        self.hip_train = os.environ.get('AGRL_HIP_TRAIN', '1') != '0'   # train-mode conv trunk (fwd + bwd) on the HIP kernels
-        self.hip_train_precision = os.environ.get('AGRL_HIP_TRAIN_PRECISION', 'fp32')   # 'fp32' exact | 'bf16x3' split-bf16 MFMA
-        self.hip_train_tail = os.environ.get('AGRL_HIP_TRAIN_TAIL', '1') != '0'         # tail of the train forward native as well
-        self._hip_packs = {}
-        # uint8 frames (B,S,3,H,W) / (B,S,H,W,3) are normalised with these -- the reference's transform_test -- inside the stem kernels
-        # (GPU eval) or in front of the path (training, CPU). Plain attributes: not parameters, not buffers, not in the state dict.
-        self.pixel_mean = (0.485, 0.456, 0.406)
-        self.pixel_std = (0.229, 0.224, 0.225)
+        init_hip_attributes(self, train=True, train_tail=True)   # MI355X path configuration (plain attributes, not part of the state dict)
 
     # ------------------------------------------------------------------ stock-torch path (CPU / train)
     def _attention_op(self, feat):

@@ -369,19 +369,38 @@ def test_attn_tail_switch_is_cached_until_reload(monkeypatch):
     assert not ops.attn_tail_supported(S, P, C, B)
 
 
-def test_weight_packs_are_cached_for_every_precision(monkeypatch):
+def _pack_tensors(obj):
+    """every tensor anywhere in a pack"""
+    import torch
+    if torch.is_tensor(obj):
+        yield obj
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            yield from _pack_tensors(v)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            yield from _pack_tensors(v)
+
+
+@pytest.mark.parametrize("name", ["vmgn", "ganet", "sta"])
+def test_weight_packs_are_cached_for_every_precision(name, monkeypatch):
     """pack_weights packs once per (device, precision) and answers from the cache while no parameter / buffer changed -- for every
     precision mode (round 6: a loop variable in the fp16x3 pack once shadowed the cache key, and every forward re-packed: correct
-    results at half the speed, visible only in the bench line). Runs without a GPU: the in-loop form of fp16x3 packs with torch ops only."""
+    results at half the speed, visible only in the bench line). Runs without a GPU: the in-loop form of fp16x3 packs with torch ops only.
+    Every model goes through the one pack cache (_resnet_hip.pack_weights) and gets its finish: after an 'fp16x3' pack no tensor of the
+    pack keeps the scaled fp32 copy it was split from (``agrl_scaled``: a second fp32 copy of every trunk weight on the device -- ganet
+    kept them until the caches were made one), and every trunk conv weight still carries its pre-scale attributes."""
     from unittest import mock
     import torch
     from recipe import recipe_state_dict
     from torchreid import hip_ops as ops
     from torchreid import models
-    from torchreid.models import _vmgn_hip as V
+    from torchreid.models import _ganet_hip, _sta_hip, _vmgn_hip
+    V = {"vmgn": _vmgn_hip, "ganet": _ganet_hip, "sta": _sta_hip}[name]
     monkeypatch.setattr(ops, "split16_planes_available", lambda: False)   # (the plane packs go through the library's pack kernels: GPU only)
-    m = models.init_model("vmgn", num_classes=4, loss={"xent", "htri"}, last_stride=1, num_split=4, num_gb=2, num_scale=1,
-                          pyramid_part=True, use_pose=True, learn_graph=True)
+    kw = dict(num_classes=4, loss={"xent", "htri"}, last_stride=1, num_split=4, num_gb=2, num_scale=1, pyramid_part=True, use_pose=True,
+              learn_graph=True)
+    m = models.init_model(name, **(dict(kw, knn=4) if name == "ganet" else kw))
     m.load_state_dict(recipe_state_dict(m.state_dict(), seed=0))
     m.eval()
     dev = torch.device("cpu")
@@ -390,6 +409,13 @@ def test_weight_packs_are_cached_for_every_precision(monkeypatch):
             p1 = V.pack_weights(m, dev, prec)
             assert V.pack_weights(m, dev, prec) is p1, prec
             assert set(m._hip_packs) >= {(0, prec)} and all(isinstance(k, tuple) for k in m._hip_packs)
+        assert not [t for t in _pack_tensors(p1) if hasattr(t, "agrl_scaled")]
+        stages = p1["trunk"] + p1.get("l4", []) + p1.get("l4_1", []) + p1.get("l4_2", [])
+        assert len(stages) == (19 if name == "vmgn" else 16)
+        for blk in stages:
+            for conv in ("c1", "c2", "c3", "ds"):
+                if blk[conv] is not None:
+                    assert hasattr(blk[conv][0], "agrl_unscale") and blk[conv][0].agrl_presplit is True, (name, conv)
         with torch.no_grad():
             m.conv1.weight.mul_(1.0)                      # an in-place edit bumps the version: the pack is rebuilt
         assert V.pack_weights(m, dev, "fp16x3") is not p1
