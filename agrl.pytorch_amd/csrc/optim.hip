@@ -1,10 +1,14 @@
 // The optimiser update of the train step (optimizer.step(), train_vidreid_xent_htri.py:411-413, built by optimizers.py:7-23) as ONE
-// multi-tensor pass: Adam / AMSGrad and SGD with momentum / Nesterov momentum over every parameter of a launch class.
+// multi-tensor pass: Adam / AMSGrad, SGD with momentum / Nesterov momentum, RMSprop, AdaBound / AMSBound and RAdam over every
+// parameter of a launch class.
 //
 //   descriptor table  kOptWords int64 words per tensor: {param, grad, state0, state1, state2, numel, vec, 0} (device memory).
 //                     Adam: state0 = exp_avg, state1 = exp_avg_sq, state2 = max_exp_avg_sq (AMSGrad, else 0);
-//                     SGD:  state0 = momentum_buffer (0 without momentum).  vec != 0: param, grad and every state pointer are
-//                     16-byte aligned (decided on the host), so every chunk start is too and the chunk takes 16-byte accesses.
+//                     SGD:  state0 = momentum_buffer (0 without momentum);
+//                     RMSprop: state0 = square_avg, state1 = momentum_buffer (0 without momentum);
+//                     AdaBound: as Adam (state2 = max_exp_avg_sq for AMSBound, else 0);  RAdam: state0 = exp_avg, state1 = exp_avg_sq.
+//                     vec != 0: param, grad and every state pointer are 16-byte aligned (decided on the host), so every chunk start
+//                     is too and the chunk takes 16-byte accesses.
 //   chunk table       int32 pairs {tensor, chunk index inside the tensor}: chunk c of tensor t covers the elements
 //                     [c * kOptChunk, min(numel, (c + 1) * kOptChunk)).
 //
@@ -19,6 +23,11 @@
 //   Adam   gd = g + wd p;  m += (1 - beta1) (gd - m);  v = beta2 v + (1 - beta2) gd^2;  [vmax = max(vmax, v), used for v below]
 //          p -= step_size m / (sqrt(v) inv_sqrt_bc2 + eps)        step_size = lr / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t)
 //   SGD    gd = g + wd p;  buf = gd (a tensor's first step) | momentum buf + gd;  d = gd + momentum buf (Nesterov) | buf;  p -= lr d
+//   RMSprop  gd = g + wd p;  sq = alpha sq + (1 - alpha) gd^2;  d = gd / (sqrt(sq) + eps);  buf = momentum buf + d, p -= lr buf | p -= lr d
+//   AdaBound gd, m, v [, vmax] as Adam;  rate = min(max(step_size / (sqrt(v) + eps), lower), upper);  p -= rate m
+//            step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t); no bias correction inside the denominator, eps after the root of the raw v
+//   RAdam    v = beta2 v + (1 - beta2) g^2;  m += (1 - beta1) (g - m);  p -= decay p;  p -= step_size m / (sqrt(v) + eps) (adaptive form)
+//            | p -= step_size m (momentum-only form); which form runs is decided per launch on the host
 // No 16-bit type in this file: both builds of the library get the same code.
 #include "agrl_common.h"
 
@@ -85,8 +94,81 @@ struct SgdOp {
         p = p - a.lr * d;
     }
 };
+struct RmspropArgs {
+    float wd, alpha, oma, eps, momentum, lr;
+};
+
+struct AdaBoundArgs {
+    float wd, omb1, beta2, omb2, step_size, eps, lower, upper;
+};
+
+struct RAdamArgs {
+    float omb1, beta2, omb2, decay, step_size, eps;
+};
+
+template <bool MOM>
+struct RmspropOp {
+    static constexpr int kStates = MOM ? 2 : 1;
+    RmspropArgs a;
+    __device__ inline void operator()(float& p, float g, float* s) const {
+        const float gd = g + a.wd * p;
+        const float sq = a.alpha * s[0] + a.oma * (gd * gd);
+        s[0] = sq;
+        float d = gd / (sqrtf(sq) + a.eps);
+        if constexpr (MOM) {
+            d = a.momentum * s[1] + d;
+            s[1] = d;
+        }
+        p = p - a.lr * d;
+    }
+};
+
+template <bool AMS>
+struct AdaBoundOp {
+    static constexpr int kStates = AMS ? 3 : 2;
+    AdaBoundArgs a;
+    __device__ inline void operator()(float& p, float g, float* s) const {
+        const float gd = g + a.wd * p;
+        const float m = s[0] + a.omb1 * (gd - s[0]);
+        float v = a.beta2 * s[1] + a.omb2 * (gd * gd);
+        s[0] = m;
+        s[1] = v;
+        if constexpr (AMS) {
+            v = fmaxf(s[2], v);
+            s[2] = v;
+        }
+        const float rate = fminf(fmaxf(a.step_size / (sqrtf(v) + a.eps), a.lower), a.upper);
+        p = p - rate * m;
+    }
+};
+
+// ADAPTIVE: the launch takes the adaptive form (N > 4), else the momentum-only form (v is still advanced)
+template <bool ADAPTIVE>
+struct RAdamOp {
+    static constexpr int kStates = 2;
+    RAdamArgs a;
+    __device__ inline void operator()(float& p, float g, float* s) const {
+        const float v = a.beta2 * s[1] + a.omb2 * (g * g);
+        const float m = s[0] + a.omb1 * (g - s[0]);
+        s[0] = m;
+        s[1] = v;
+        const float pd = p - a.decay * p;
+        if constexpr (ADAPTIVE) {
+            p = pd - a.step_size * m / (sqrtf(v) + a.eps);
+        } else {
+            p = pd - a.step_size * m;
+        }
+    }
+};
+
 template <bool AMS>
 constexpr bool loads_state(const AdamOp<AMS>&) { return true; }
+template <bool MOM>
+constexpr bool loads_state(const RmspropOp<MOM>&) { return true; }
+template <bool AMS>
+constexpr bool loads_state(const AdaBoundOp<AMS>&) { return true; }
+template <bool ADAPTIVE>
+constexpr bool loads_state(const RAdamOp<ADAPTIVE>&) { return true; }
 template <int MODE>
 constexpr bool loads_state(const SgdOp<MODE>&) { return SgdOp<MODE>::kLoadState; }
 
@@ -251,4 +333,37 @@ extern "C" int agrl_sgd_step(const void* tensors, int n_tensors, const void* chu
     if (!has_momentum) return launch("agrl_sgd_step", tensors, chunks, n_chunks, SgdOp<0>{a}, zero_grad, stream);
     if (first_step) return launch("agrl_sgd_step", tensors, chunks, n_chunks, SgdOp<1>{a}, zero_grad, stream);
     return launch("agrl_sgd_step", tensors, chunks, n_chunks, SgdOp<2>{a}, zero_grad, stream);
+}
+
+#define AGRL_OPTIM_TABLE_CHECKS(fn)                                                                                                  \
+    AGRL_CHECK_ARG(tensors && chunks, fn ": null pointer");                                                                          \
+    AGRL_CHECK_ARG(n_tensors > 0 && n_chunks >= n_tensors, fn ": need n_tensors > 0 and at least one chunk per tensor");             \
+    AGRL_CHECK_ARG((((uintptr_t)tensors) & 7) == 0 && (((uintptr_t)chunks) & 7) == 0, fn ": tables must be 8-byte aligned")
+
+extern "C" int agrl_rmsprop_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay, float alpha,
+                                 float one_minus_alpha, float eps, float momentum, float lr, int has_momentum, int zero_grad,
+                                 agrl_stream_t stream) {
+    AGRL_OPTIM_TABLE_CHECKS("agrl_rmsprop_step");
+    const RmspropArgs a = {weight_decay, alpha, one_minus_alpha, eps, momentum, lr};
+    if (has_momentum) return launch("agrl_rmsprop_step", tensors, chunks, n_chunks, RmspropOp<true>{a}, zero_grad, stream);
+    return launch("agrl_rmsprop_step", tensors, chunks, n_chunks, RmspropOp<false>{a}, zero_grad, stream);
+}
+
+extern "C" int agrl_adabound_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay,
+                                  float one_minus_beta1, float beta2, float one_minus_beta2, float step_size, float eps, float lower,
+                                  float upper, int amsbound, int zero_grad, agrl_stream_t stream) {
+    AGRL_OPTIM_TABLE_CHECKS("agrl_adabound_step");
+    AGRL_CHECK_ARG(lower <= upper, "agrl_adabound_step: need lower <= upper");
+    const AdaBoundArgs a = {weight_decay, one_minus_beta1, beta2, one_minus_beta2, step_size, eps, lower, upper};
+    if (amsbound) return launch("agrl_adabound_step", tensors, chunks, n_chunks, AdaBoundOp<true>{a}, zero_grad, stream);
+    return launch("agrl_adabound_step", tensors, chunks, n_chunks, AdaBoundOp<false>{a}, zero_grad, stream);
+}
+
+extern "C" int agrl_radam_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float one_minus_beta1, float beta2,
+                               float one_minus_beta2, float decay, float step_size, float eps, int adaptive, int zero_grad,
+                               agrl_stream_t stream) {
+    AGRL_OPTIM_TABLE_CHECKS("agrl_radam_step");
+    const RAdamArgs a = {one_minus_beta1, beta2, one_minus_beta2, decay, step_size, eps};
+    if (adaptive) return launch("agrl_radam_step", tensors, chunks, n_chunks, RAdamOp<true>{a}, zero_grad, stream);
+    return launch("agrl_radam_step", tensors, chunks, n_chunks, RAdamOp<false>{a}, zero_grad, stream);
 }

@@ -158,6 +158,9 @@ SIGNATURES = {
     "agrl_optim_geometry": [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "agrl_adam_step": [_p, _i, _p, _i] + [_f] * 7 + [_i, _i, _p],
     "agrl_sgd_step": [_p, _i, _p, _i, _f, _f, _f, _i, _i, _i, _i, _p],
+    "agrl_rmsprop_step": [_p, _i, _p, _i] + [_f] * 6 + [_i, _i, _p],
+    "agrl_adabound_step": [_p, _i, _p, _i] + [_f] * 8 + [_i, _i, _p],
+    "agrl_radam_step": [_p, _i, _p, _i] + [_f] * 6 + [_i, _i, _p],
 }
 
 _lock = threading.Lock()

@@ -1930,6 +1930,30 @@ def sgd_step(tensors, chunks, weight_decay, momentum, lr, has_momentum, first_st
              1 if first_step else 0, 1 if nesterov else 0, 1 if zero_grad else 0, _stream(tensors))
 
 
+def rmsprop_step(tensors, chunks, weight_decay, alpha, one_minus_alpha, eps, momentum, lr, has_momentum, zero_grad):
+    """One multi-tensor RMSprop update in place (not centered; momentum optional). optimizers.py:16-17."""
+    with _dev(tensors):
+        call("agrl_rmsprop_step", *_optim_tables(tensors, chunks), float(weight_decay), float(alpha), float(one_minus_alpha), float(eps),
+             float(momentum), float(lr), 1 if has_momentum else 0, 1 if zero_grad else 0, _stream(tensors))
+
+
+def adabound_step(tensors, chunks, weight_decay, one_minus_beta1, beta2, one_minus_beta2, step_size, eps, lower, upper, amsbound, zero_grad):
+    """One multi-tensor AdaBound / AMSBound update in place; step_size, lower and upper are the step's constants
+    (hip_optim.adabound_constants). optimizers.py:26-138."""
+    with _dev(tensors):
+        call("agrl_adabound_step", *_optim_tables(tensors, chunks), float(weight_decay), float(one_minus_beta1), float(beta2),
+             float(one_minus_beta2), float(step_size), float(eps), float(lower), float(upper), 1 if amsbound else 0, 1 if zero_grad else 0,
+             _stream(tensors))
+
+
+def radam_step(tensors, chunks, one_minus_beta1, beta2, one_minus_beta2, decay, step_size, eps, adaptive, zero_grad):
+    """One multi-tensor RAdam update in place; step_size and the form (adaptive or momentum-only) are the step's constants
+    (hip_optim.radam_constants). optimizers.py:141-211."""
+    with _dev(tensors):
+        call("agrl_radam_step", *_optim_tables(tensors, chunks), float(one_minus_beta1), float(beta2), float(one_minus_beta2),
+             float(decay), float(step_size), float(eps), 1 if adaptive else 0, 1 if zero_grad else 0, _stream(tensors))
+
+
 # ---- tails of the STA baselines (csrc/sta.hip) --------------------------------------------------------------------------------
 STA_PARTS = 4
 LINEAR_BN_RELU_MAX_M = 32   # AGRL_LINEAR_BN_RELU_MAX_M: the rows of x the kernel's LDS staging holds

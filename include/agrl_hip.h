@@ -826,6 +826,38 @@ int agrl_adam_step(const void* tensors, int n_tensors, const void* chunks, int n
 int agrl_sgd_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay, float momentum,
                   float lr, int has_momentum, int first_step, int nesterov, int zero_grad, agrl_stream_t stream);
 
+/* RMSprop (torch.optim.RMSprop, not centered; optimizers.py:16-17). state0 = square_avg, state1 = momentum_buffer (has_momentum
+ * only, else 0). Per element in this order, IEEE division and square root:
+ *   gd = g + weight_decay p;  sq = alpha sq + one_minus_alpha gd^2;  d = gd / (sqrt(sq) + eps);
+ *   has_momentum: buf = momentum buf + d, p -= lr buf;  otherwise p -= lr d
+ * A momentum buffer the caller created for this step holds zeros: there is no first-step form. */
+int agrl_rmsprop_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay, float alpha,
+                      float one_minus_alpha, float eps, float momentum, float lr, int has_momentum, int zero_grad,
+                      agrl_stream_t stream);
+
+/* AdaBound / AMSBound (optimizers.py:26-138). state0 = exp_avg, state1 = exp_avg_sq, state2 = max_exp_avg_sq (amsbound only,
+ * else 0). Per element in this order, IEEE division and square root:
+ *   gd = g + weight_decay p;  m += one_minus_beta1 (gd - m);  v = beta2 v + one_minus_beta2 gd^2;
+ *   amsbound: vmax = max(vmax, v), used for v below;  rate = min(max(step_size / (sqrt(v) + eps), lower), upper);  p -= rate m
+ * with, for the step count t of EVERY tensor of the launch, step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t),
+ * lower = final (1 - 1 / (gamma t + 1)), upper = final (1 + 1 / (gamma t)), final = final_lr lr / base_lr. The denominator
+ * carries no bias correction and eps is added after the root of the raw v (the reference's rule, not Adam's). lower <= upper. */
+int agrl_adabound_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float weight_decay,
+                       float one_minus_beta1, float beta2, float one_minus_beta2, float step_size, float eps, float lower,
+                       float upper, int amsbound, int zero_grad, agrl_stream_t stream);
+
+/* RAdam (optimizers.py:141-211). state0 = exp_avg, state1 = exp_avg_sq; the gradient takes no weight decay. Per element in this
+ * order, IEEE division and square root:
+ *   v = beta2 v + one_minus_beta2 g^2;  m += one_minus_beta1 (g - m);  p -= decay p        (decay = weight_decay lr, 0 without)
+ *   adaptive: p -= step_size m / (sqrt(v) + eps);  otherwise (momentum-only form): p -= step_size m
+ * For the step count t of EVERY tensor of the launch the caller forms N_max = 2 / (1 - beta2) - 1,
+ * N = N_max - 2 t beta2^t / (1 - beta2^t), step_size = lr sqrt((1 - beta2^t) (N - 4) / (N_max - 4) (N - 2) / N N_max / (N_max - 2))
+ * / (1 - beta1^t) when N > 5, else lr / (1 - beta1^t), and adaptive = N > 4: for 4 < N <= 5 the adaptive form runs with the
+ * unrectified step size, as in the reference. */
+int agrl_radam_step(const void* tensors, int n_tensors, const void* chunks, int n_chunks, float one_minus_beta1, float beta2,
+                    float one_minus_beta2, float decay, float step_size, float eps, int adaptive, int zero_grad,
+                    agrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
