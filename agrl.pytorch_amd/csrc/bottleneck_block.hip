@@ -15,7 +15,8 @@
 //   * 3x3 sweep straight from the patch with the conflict-free column permutation (frag_px / patch_off, igemm_dev.h)
 //   * the next tile's patch is prefetched one tile ahead (LDS-DMA, double-buffered); the residual tile is requested at the
 //     top of its own tile and lands under the 3x3 sweep; waits are counted (loads and stores retire in order)
-#include "igemm_dev.h"
+//   * everything behind the second GEMM is a stage of bneck_dev.h, shared with bottleneck_tail.hip
+#include "bneck_dev.h"
 
 namespace {
 
@@ -70,60 +71,29 @@ __global__ __launch_bounds__(512) void bottleneck_block_kernel(const BlockParams
         const int row = wave * 8 + lrow;
 #pragma unroll
         for (int t = 0; t < 9; ++t)
-            dma16(reinterpret_cast<const unsigned char*>(p.w2) + ((size_t)row * 576 + t * 64) * 2 + ((lchk ^ ((row >> 1) & 7)) << 4),
-                  s_w2 + t * W_TAP + wave * 8 * 128);
+            bneck_dma_rows(reinterpret_cast<const unsigned char*>(p.w2) + ((size_t)row * 576 + t * 64) * 2, true, row, lchk, s_w2 + t * W_TAP + wave * 8 * 128);
     }
     // ---- 1x1 weights as MFMA A fragments in registers. GEMM 1 (64 px x 256 ch): wave grid 2 (px) x 4 (ch), wave tile
     // 32 px x 64 ch; GEMM 2 (64 px x CN ch, K = 256): same grid, wave tile 32 px x CN/4 ch
     const int wm2 = wave & 1, wn4 = wave >> 1;
     uint4 w3f[4][2], wsf[CAT ? 4 : 1][2], w1f[NA2][8];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const size_t o = ((size_t)(wn4 * 64 + a * 16 + frow) * 64 + kk * 32 + fchunk * 8) * 2;
-            w3f[a][kk] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(p.w3) + o);
-            if constexpr (CAT) wsf[a][kk] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(p.ws) + o);
-        }
-#pragma unroll
-    for (int a = 0; a < NA2; ++a)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-            w1f[a][ks] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(p.w1n) +
-                                                         ((size_t)(wn4 * (CN / 4) + a * 16 + frow) * 256 + ks * 32 + fchunk * 8) * 2);
+    bneck_wfrags(w3f, p.w3, wn4 * 64 + frow, 64, fchunk);
+    if constexpr (CAT) bneck_wfrags(wsf, p.ws, wn4 * 64 + frow, 64, fchunk);
+    bneck_wfrags(w1f, p.w1n, wn4 * (CN / 4) + frow, 256, fchunk);
     // biases of this lane's output channels
     const int wm = wave & 3, wn = wave >> 2;  // GEMM 0 (3x3, 64 px x 64 ch): wave grid 4 (px) x 2 (ch), wave tile 16 px x 32 ch
-    float4 b2v[2], b3v[4], b1v[NA2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) b2v[a] = *reinterpret_cast<const float4*>(p.b2 + wn * 32 + a * 16 + fchunk * 4);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        b3v[a] = *reinterpret_cast<const float4*>(p.b3 + wn4 * 64 + a * 16 + fchunk * 4);
-        if constexpr (CAT) {
-            const float4 t = *reinterpret_cast<const float4*>(p.bs + wn4 * 64 + a * 16 + fchunk * 4);
-            b3v[a].x += t.x; b3v[a].y += t.y; b3v[a].z += t.z; b3v[a].w += t.w;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < NA2; ++a) b1v[a] = *reinterpret_cast<const float4*>(p.b1n + wn4 * (CN / 4) + a * 16 + fchunk * 4);
+    float b2v[2][4], b3v[4][4], b1v[NA2][4];
+    bneck_bias<false>(b2v, p.b2, wn * 32 + fchunk * 4);
+    bneck_bias<false>(b3v, p.b3, wn4 * 64 + fchunk * 4);
+    if constexpr (CAT) bneck_bias<true>(b3v, p.bs, wn4 * 64 + fchunk * 4);
+    bneck_bias<false>(b1v, p.b1n, wn4 * (CN / 4) + fchunk * 4);
     // pin everything loaded so far: re-loading inside the tile loop would come with vmcnt(0) waits that drain the DMA queue
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            asm volatile("" : "+v"(w3f[a][kk].x), "+v"(w3f[a][kk].y), "+v"(w3f[a][kk].z), "+v"(w3f[a][kk].w));
-            if constexpr (CAT) asm volatile("" : "+v"(wsf[a][kk].x), "+v"(wsf[a][kk].y), "+v"(wsf[a][kk].z), "+v"(wsf[a][kk].w));
-        }
-#pragma unroll
-    for (int a = 0; a < NA2; ++a)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) asm volatile("" : "+v"(w1f[a][ks].x), "+v"(w1f[a][ks].y), "+v"(w1f[a][ks].z), "+v"(w1f[a][ks].w));
-#pragma unroll
-    for (int a = 0; a < 4; ++a) asm volatile("" : "+v"(b3v[a].x), "+v"(b3v[a].y), "+v"(b3v[a].z), "+v"(b3v[a].w));
-#pragma unroll
-    for (int a = 0; a < 2; ++a) asm volatile("" : "+v"(b2v[a].x), "+v"(b2v[a].y), "+v"(b2v[a].z), "+v"(b2v[a].w));
-#pragma unroll
-    for (int a = 0; a < NA2; ++a) asm volatile("" : "+v"(b1v[a].x), "+v"(b1v[a].y), "+v"(b1v[a].z), "+v"(b1v[a].w));
+    bneck_pin(w3f);
+    if constexpr (CAT) bneck_pin(wsf);
+    bneck_pin(w1f);
+    bneck_pin(b3v);
+    bneck_pin(b2v);
+    bneck_pin(b1v);
 
     // per-lane parts of the residual-tile and out-tile global offsets (pixel (row >> 3, row & 7) of the tile and the
     // swizzled chunk), computed ONCE; per tile only the tile's base pixel (uniform) is added
@@ -168,11 +138,10 @@ __global__ __launch_bounds__(512) void bottleneck_block_kernel(const BlockParams
         asm volatile("" : "+v"(ln));
         if constexpr (CAT) {
             const int row = wave * 8 + (ln >> 3);
-            dma16(xsg + gpix(img, oy0, ox0, row) * 128 + (((ln & 7) ^ ((row >> 1) & 7)) << 4), s_x + wave * 1024);
+            bneck_dma_rows(xsg + gpix(img, oy0, ox0, row) * 128, true, row, ln & 7, s_x + wave * 1024);
         } else {
             const unsigned char* tbase = resg + gpix(img, oy0, ox0, 0) * 512;  // uniform
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dma16(tbase + res_lane[j], s_r + (wave * 4 + j) * 1024);
+            bneck_dma_tile<512, 4>(s_r, wave, ln, [&](int j, int, int) { return tbase + res_lane[j]; });
         }
     };
 
@@ -246,8 +215,8 @@ __global__ __launch_bounds__(512) void bottleneck_block_kernel(const BlockParams
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const int c = wn * 32 + a * 16 + fc * 4;
-                float v[4] = {relu_nan(acc0[a][0] + b2v[a].x), relu_nan(acc0[a][1] + b2v[a].y),
-                              relu_nan(acc0[a][2] + b2v[a].z), relu_nan(acc0[a][3] + b2v[a].w)};
+                float v[4] = {relu_nan(acc0[a][0] + b2v[a][0]), relu_nan(acc0[a][1] + b2v[a][1]),
+                              relu_nan(acc0[a][2] + b2v[a][2]), relu_nan(acc0[a][3] + b2v[a][3])};
                 store4<lp16_t>(reinterpret_cast<lp16_t*>(s_y + prow * 128 + (((c >> 3) ^ ((prow >> 1) & 7)) << 4) + ((c & 4) << 1)), v);
             }
         }
@@ -289,105 +258,30 @@ __global__ __launch_bounds__(512) void bottleneck_block_kernel(const BlockParams
             else wait_vmcnt<0>();
             wg_barrier();                    // everybody's residual pieces are in the out tile
         }
-        // bias + residual (in place) + ReLU -> bf16 out tile; all eight residual cells are read before the first is
-        // written back (a read behind a write to the same array is not hoisted by the compiler: eight LDS round trips)
-        uint2 rcell[2][4];
-        if constexpr (!CAT) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int px = wm2 * 32 + b * 16 + fr;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const int c = wn4 * 64 + a * 16 + fc * 4;
-                    rcell[b][a] = *reinterpret_cast<const uint2*>(s_r + px * 512 + (((c >> 3) ^ (px & 31)) << 4) + ((c & 4) << 1));
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int px = wm2 * 32 + b * 16 + fr;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const int c = wn4 * 64 + a * 16 + fc * 4;
-                unsigned char* cell = s_r + px * 512 + (((c >> 3) ^ (px & 31)) << 4) + ((c & 4) << 1);
-                float rr[4] = {0.f, 0.f, 0.f, 0.f};
-                if constexpr (!CAT) {
-                    unpack_lp16x2(rcell[b][a].x, rr[0], rr[1]);
-                    unpack_lp16x2(rcell[b][a].y, rr[2], rr[3]);
-                }
-                float v[4];
-                v[0] = relu_nan(acc[a][b][0] + b3v[a].x + rr[0]);
-                v[1] = relu_nan(acc[a][b][1] + b3v[a].y + rr[1]);
-                v[2] = relu_nan(acc[a][b][2] + b3v[a].z + rr[2]);
-                v[3] = relu_nan(acc[a][b][3] + b3v[a].w + rr[3]);
-                store4<lp16_t>(reinterpret_cast<lp16_t*>(cell), v);
-            }
-        }
+        bneck_out_tile<!CAT, 512>(s_r, acc, b3v, wm2 * 32 + fr, wn4 * 64 + fc * 4);
         wg_barrier();  // out tile complete
         // drain the out tile: 2048 16-byte chunks, 4 per thread, whole 512-byte rows per 32 lanes
         {
             unsigned char* obase = reinterpret_cast<unsigned char*>(p.out) + gpix(img, oy0, ox0, 0) * 512;  // uniform
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = (td >> 5) + 16 * i;
-                const int pch = td & 31;
-                const uint4 v = *reinterpret_cast<const uint4*>(s_r + row * 512 + (pch << 4));
-                if constexpr (CN == 64) *reinterpret_cast<uint4*>(obase + out_lane[i]) = v;  // (CN 128: no registers to spare)
-                else *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(p.out) + (gpix(img, oy0, ox0, row) * 256 + (pch ^ (row & 31)) * 8) * 2) = v;
-            }
+            bneck_drain<512, 4, 16, 0>(s_r, td >> 5, td & 31, [&](int i, int row, int gch, unsigned char*& g) {
+                if constexpr (CN == 64) g = obase + out_lane[i];  // (CN 128: no registers to spare)
+                else g = reinterpret_cast<unsigned char*>(p.out) + (gpix(img, oy0, ox0, row) * 256 + gch * 8) * 2;
+                return true;
+            });
         }
         // ---- GEMM 2: 64 px x CN ch, K = 256, B operand straight from the out tile. Wave tile 32 px x CN/4 ch.
         f32x4_t acc2[NA2][2];
-#pragma unroll
-        for (int a = 0; a < NA2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc2[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        {
-            uint4 x2[3][2];  // fragments two k-steps ahead of the MFMAs
-            auto ld2 = [&](int ks, int slot) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int px = wm2 * 32 + b * 16 + fr;
-                    x2[slot][b] = *reinterpret_cast<const uint4*>(s_r + px * 512 + (((ks * 4 + fc) ^ (px & 31)) << 4));
-                }
-            };
-            ld2(0, 0);
-            ld2(1, 1);
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                if (ks + 2 < 8) ld2(ks + 2, (ks + 2) % 3);
-#pragma unroll
-                for (int a = 0; a < NA2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc2[a][b] = Frag<lp16_t>::mma(w1f[a][ks], x2[ks % 3][b], acc2[a][b]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        bneck_gemm2<512, 2>(s_r, wm2 * 32 + fr, fc, acc2, [&](int a, int ks) { return w1f[a][ks]; });  // fragments two k-steps ahead of the MFMAs
         // z' tile: CN == 64 -> the y2 tile (every read of it was before the last barrier), 128-byte rows;
         //          CN == 128 -> over the out tile once every wave has finished reading it, 256-byte rows
         unsigned char* sz = CN == 64 ? s_y : s_r;
         if constexpr (CN == 128) wg_barrier();
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int px = wm2 * 32 + b * 16 + fr;
-#pragma unroll
-            for (int a = 0; a < NA2; ++a) {
-                const int c = wn4 * (CN / 4) + a * 16 + fc * 4;
-                float v[4];
-                v[0] = relu_nan(acc2[a][b][0] + b1v[a].x);
-                v[1] = relu_nan(acc2[a][b][1] + b1v[a].y);
-                v[2] = relu_nan(acc2[a][b][2] + b1v[a].z);
-                v[3] = relu_nan(acc2[a][b][3] + b1v[a].w);
-                store4<lp16_t>(reinterpret_cast<lp16_t*>(sz + px * (CN * 2) + (((c >> 3) ^ (px & (CN / 8 - 1))) << 4) + ((c & 4) << 1)), v);
-            }
-        }
+        bneck_z_tile<CN>(sz, acc2, b1v, wm2 * 32 + fr, wn4 * (CN / 4) + fc * 4);
         wg_barrier();  // z' tile complete (CN == 64: and every read of the out tile done)
-#pragma unroll
-        for (int i = 0; i < CN / 64; ++i) {
-            const int row = td >> 3, pch = (td & 7) * (CN / 64) + i;
-            const uint4 v = *reinterpret_cast<const uint4*>(sz + row * (CN * 2) + (pch << 4));
-            *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(p.zn) + (gpix(img, oy0, ox0, row) * CN + (pch ^ (row & (CN / 8 - 1))) * 8) * 2) = v;
-        }
+        bneck_drain<2 * CN, NA2, 0, 1>(sz, td >> 3, (td & 7) * NA2, [&](int, int row, int gch, unsigned char*& g) {
+            g = reinterpret_cast<unsigned char*>(p.zn) + (gpix(img, oy0, ox0, row) * CN + gch * 8) * 2;
+            return true;
+        });
         // the top of the next iteration waits for the next patch (older than these NST stores) and its barrier keeps the
         // next residual from landing on a tile somebody still reads
     }
@@ -399,23 +293,18 @@ extern "C" int agrl_bottleneck_block(const void* z, const void* w2, const float*
                                      const void* residual, const void* x_short, const void* w_short, const float* b_short,
                                      void* out, const void* w1_next, const float* b1_next, void* z_next, int F, int H, int W,
                                      int Cmid, int Cout, int Cnext, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(z && w2 && b2 && w3 && b3 && out && w1_next && b1_next && z_next, "agrl_bottleneck_block: null pointer");
-    AGRL_CHECK_ARG((residual != nullptr) != (x_short != nullptr),
-                   "agrl_bottleneck_block: pass either the residual map or the downsample conv's input, not both");
-    AGRL_CHECK_ARG(!x_short || (w_short && b_short), "agrl_bottleneck_block: the downsample form needs its weights and bias");
+    static const char* who = "agrl_bottleneck_block";
+    if (int e = bneck_check_operands(who, {z, w2, b2, w3, b3, out, w1_next, b1_next, z_next}, residual, x_short, w_short, b_short)) return e;
     AGRL_CHECK_ARG(F > 0 && H > 0 && W > 0 && (H % 8) == 0 && (W % 8) == 0, "agrl_bottleneck_block: maps must be multiples of 8 x 8 (got %d x %d)", H, W);
     AGRL_CHECK_ARG(Cmid == 64 && Cout == 256 && (Cnext == 64 || (Cnext == 128 && !x_short)),
                    "agrl_bottleneck_block: built for Cmid=64, Cout=256, Cnext=64 (128 without downsample), got %d/%d/%d", Cmid, Cout, Cnext);
     AGRL_CHECK_ARG((size_t)F * H * W * 256 * 2 < (1ull << 40), "agrl_bottleneck_block: problem too large");
-    const uintptr_t al = (uintptr_t)z | (uintptr_t)w2 | (uintptr_t)b2 | (uintptr_t)w3 | (uintptr_t)b3 | (uintptr_t)residual |
-                         (uintptr_t)x_short | (uintptr_t)w_short | (uintptr_t)b_short | (uintptr_t)out | (uintptr_t)w1_next |
-                         (uintptr_t)b1_next | (uintptr_t)z_next;
-    AGRL_CHECK_ARG((al & 15) == 0, "agrl_bottleneck_block: pointers must be 16-byte aligned");
+    if (int e = bneck_check_aligned(who, {z, w2, b2, w3, b3, residual, x_short, w_short, b_short, out, w1_next, b1_next, z_next})) return e;
     BlockParams p;
     p.z = z; p.w2 = w2; p.b2 = b2; p.w3 = w3; p.b3 = b3; p.res = residual; p.xs = x_short; p.ws = w_short; p.bs = b_short;
     p.out = out; p.w1n = w1_next; p.b1n = b1_next; p.zn = z_next; p.F = F; p.H = H; p.W = W;
     const int ntiles = F * (H / 8) * (W / 8);
-    const int grid = ntiles < 256 ? ntiles : 256;
+    const int grid = bneck_grid(ntiles);
     if (x_short) hipLaunchKernelGGL((bottleneck_block_kernel<true, 64>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p, ntiles);
     else if (Cnext == 128) hipLaunchKernelGGL((bottleneck_block_kernel<false, 128>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p, ntiles);
     else hipLaunchKernelGGL((bottleneck_block_kernel<false, 64>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p, ntiles);

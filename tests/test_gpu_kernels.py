@@ -268,11 +268,15 @@ def test_conv_wide_tile(case, tile, monkeypatch):
 
 
 @pytest.mark.parametrize("cnext", [64, 128])
-@pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 10, 7), (5, 64, 32)])
+@pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 10, 7), (5, 64, 32), (9, 64, 32), (7, 50, 47)])
 def test_bottleneck_tail(shape, cnext):
     """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; z from the rounded out.
     conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_tail.hip) against the
-    two separate igemm launches (bitwise: same fp32 accumulation order, same roundings) and the fp32 reference."""
+    two separate igemm launches (bitwise: same fp32 accumulation order, same roundings) and the fp32 reference.
+    (9, 64, 32) = 288 tiles, more than one per workgroup (prefetch slot flip, counted waits, the barrier that keeps the
+    next tile's DMA off a tile still being read); (7, 50, 47) = 258 tiles with a last tile of 2 rows: both at once.
+    The first-block form (shortcut conv in the same pass) has no separate-launch twin with the same roundings: bitwise
+    against bottleneck_block's first-block form where the map divides into 8 x 8 tiles, element bounds elsewhere."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(N * H)
@@ -313,15 +317,33 @@ def test_bottleneck_tail(shape, cnext):
     e1, e2 = rel_err(out.float().permute(0, 3, 1, 2), out_ref), rel_err(z.float().permute(0, 3, 1, 2), z_ref)
     print("bottleneck tail + downsample", shape, "out %.3e z %.3e" % (e1, e2))
     assert e1 < 1e-2 and e2 < 1e-2
+    dsc = (nhwc(x0, LP_DTYPE), ws.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV), bs.to(DEV))
+    if H % 8 or W % 8:
+        # one GEMM over the concatenated channels, the two biases summed in fp32 first (what the kernel holds)
+        check_conv(out, torch.cat([y2, x0], 1), torch.cat([w3, ws], 1), b3 + bs, relu=True, name="tail + downsample out %s" % (shape,))
+        check_conv(z, out.float().permute(0, 3, 1, 2).cpu(), w1, b1, relu=True, name="tail + downsample z %s" % (shape,))
+        return
+    # the whole-block kernel's first-block form on the same roundings: y2 = its 3x3 stage, from the separate launch
+    zin = torch.randn((N, 64, H, W), generator=g).to(LP_DTYPE).float()
+    w2 = (torch.randn((64, 64, 3, 3), generator=g) / 24).to(LP_DTYPE).float()
+    b2 = torch.randn(64, generator=g)
+    dzin, dw2 = nhwc(zin, LP_DTYPE), w2.permute(0, 2, 3, 1).contiguous().to(LP_DTYPE).to(DEV)
+    y2s = ops.conv_bn_act(dzin, dw2, b2.to(DEV), 1, 1, True)
+    with poisoned_outputs():
+        out_t, z_t = ops.bottleneck_tail(y2s, dw3, b3.to(DEV), None, dw1, b1.to(DEV), shortcut=dsc)
+    out_b, z_b = ops.bottleneck_block(dzin, dw2, b2.to(DEV), dw3, b3.to(DEV), None, dw1, b1.to(DEV), shortcut=dsc)
+    torch.cuda.synchronize()
+    assert torch.equal(out_t, out_b) and torch.equal(z_t, z_b)
 
 
 @pytest.mark.parametrize("cnext", [64, 128])
-@pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 8, 24), (9, 64, 32)])
+@pytest.mark.parametrize("shape", [(2, 64, 32), (1, 16, 8), (3, 8, 24), (9, 64, 32), (5, 64, 32)])
 def test_bottleneck_block(shape, cnext, monkeypatch):
     """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; each from the rounded last.
     3x3 conv + conv3 + residual + relu of a layer-1 block fused with the next block's conv1 (bottleneck_block.hip)
     against the three separate launches (bitwise: same fp32 accumulation order, same roundings) and the fp32 reference;
-    (9, 64, 32) = 288 tiles, more than one per workgroup; also the first-block form with the downsample conv."""
+    (9, 64, 32) = 288 tiles, more than one per workgroup, (5, 64, 32) = 160 tiles, fewer workgroups than CUs; also the
+    first-block form with the downsample conv."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(N * H + cnext)
@@ -369,12 +391,13 @@ def test_bottleneck_block(shape, cnext, monkeypatch):
     assert torch.equal(out, out3) and torch.equal(zn, z3)
 
 
-@pytest.mark.parametrize("shape", [(2, 32, 16), (1, 16, 8), (3, 10, 7), (40, 32, 16)])
+@pytest.mark.parametrize("shape", [(2, 32, 16), (1, 16, 8), (3, 10, 7), (40, 32, 16), (7, 50, 47)])
 def test_bottleneck_tail_layer2(shape):
     """Each stage: 16-bit operands, fp32 accumulation, (acc + bias) + residual, ReLU, one RNE rounding; z from the rounded out.
     Layer-2 form of the fused tail (conv3 128 -> 512 + residual + relu, next conv1 512 -> 128; weights resident in
     registers) against the two separate igemm launches (bitwise) and the fp32 reference; (40, 32, 16) = 320 tiles, more
-    than one per workgroup (prefetch ring, counted waits), (3, 10, 7) a ragged last tile."""
+    than one per workgroup (prefetch ring, counted waits), (3, 10, 7) a ragged last tile, (7, 50, 47) = 258 tiles with a
+    last tile of 2 rows: both at once."""
     from torchreid import hip_ops as ops
     N, H, W = shape
     g = torch.Generator().manual_seed(N * H + 7)
