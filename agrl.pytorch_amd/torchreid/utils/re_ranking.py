@@ -6,12 +6,22 @@ procedure runs on the device (``agrl_re_ranking``: joint distance matrix, exact 
 k-reciprocal expansion, local query expansion, Jaccard distance -- four dense (m+n)^2 fp32 matrices in HBM instead of
 the reference's Python loops); CUDA tensors are accepted as well and then a CUDA tensor is returned. Without any GPU the
 numpy host code below evaluates the same procedure (the reference's own CPU-runnable configuration).
+
+The kernel states limits the reference does not have: ``1 <= k1 <= 30``, ``k2 <= k1 + 1`` and ``m + n <= 16384``
+(``hip_ops.re_ranking`` stays strict and raises ``HipKernelError`` beyond them). This drop-in accepts what the reference
+accepts: a call with ``k1 > 30``, ``k2 > k1 + 1`` or ``m + n > 16384`` is evaluated by the host code below, on a GPU host
+too (CUDA tensors are copied to the host and a CUDA tensor is returned). That is a stated route for the rare settings,
+not a fall-back for a missing kernel: a call inside the limits never takes it.
 """
 from __future__ import absolute_import
 from __future__ import division
 
 import numpy as np
 import torch
+
+
+KERNEL_MAX_K1 = 30            # agrl_re_ranking: a wavefront holds one neighbour list
+KERNEL_MAX_SAMPLES = 16384    # ... and a workgroup of rr_jaccard one row of m + n sums in registers
 
 
 def _re_ranking_host(q_g, q_q, g_g, k1, k2, lambda_value):
@@ -53,9 +63,13 @@ def _re_ranking_host(q_g, q_q, g_g, k1, k2, lambda_value):
 def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3):
     tensors = [isinstance(a, torch.Tensor) for a in (q_g_dist, q_q_dist, g_g_dist)]
     on_device = all(tensors) and q_g_dist.is_cuda
-    if not (on_device or torch.cuda.is_available()):
-        arrs = [(a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float32) for a in (q_g_dist, q_q_dist, g_g_dist)]
-        return _re_ranking_host(arrs[0], arrs[1], arrs[2], k1, k2, lambda_value)
+    m, n = q_g_dist.shape if hasattr(q_g_dist, 'shape') else np.shape(q_g_dist)
+    beyond_kernel = k1 > KERNEL_MAX_K1 or k2 > k1 + 1 or m + n > KERNEL_MAX_SAMPLES
+    if beyond_kernel or not (on_device or torch.cuda.is_available()):
+        arrs = [(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float32)
+                for a in (q_g_dist, q_q_dist, g_g_dist)]
+        out = np.ascontiguousarray(_re_ranking_host(arrs[0], arrs[1], arrs[2], k1, k2, lambda_value), dtype=np.float32)
+        return torch.from_numpy(out).to(q_g_dist.device) if on_device else out
     from torchreid import _hip, hip_ops as ops
     _hip.lib()
     dev = q_g_dist.device if on_device else torch.device('cuda', torch.cuda.current_device())
