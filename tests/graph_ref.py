@@ -180,9 +180,9 @@ def linear_mix_ref(P, W, f, scale, shift, keep, gamma, slope, mode, rows=None):
     as float; 'fp16x3': W and scale WITHOUT the power-of-two pre-scale, which is exact) -> exact, mag, n_acc, slack.
     n_acc = bounds.n_acc_for(K, 4 | 16) + 4: the k-chain (exact-fp32 MFMA: 4 deep; 16-bit MFMA: 16 per lane group; the two k-halves
     of graph_linear_kernel meet in one addition, inside n_acc_for's slack) and the epilogue's slope, keep f, gamma y and sum.
-    Split modes: every product carries train_ref.C_SPLIT |p| |w| (the bound of test_bounds.py's split recipe; fp16 halves keep 11
-    bits, so the fp16 split sits far inside the bf16 constant as long as the low halves stay above fp16's subnormal step 2^-24 in
-    the sum, which operands of order one do): slack = C_SPLIT |gamma| |scale| (|P| |W|^T). ``rows``: optional row subset of M."""
+    Split modes: every product carries C |p| |w|: slack = C |gamma| |scale| (|P| |W|^T) with C = train_ref.C_SPLIT for 'bf16x3' (the
+    bound of test_bounds.py's split recipe) and, for 'fp16x3', split16_ref.C_SPLIT16 plus that module's absolute terms for low halves
+    that are not normal fp16 numbers (P split in the k-loop, W pre-scaled and split at pack time). ``rows``: optional row subset of M."""
     from train_ref import C_SPLIT
     assert mode in LINEAR_MODES
     K = P.shape[-1]
@@ -195,8 +195,16 @@ def linear_mix_ref(P, W, f, scale, shift, keep, gamma, slope, mode, rows=None):
     pre = acc * sc + sh
     y = torch.where(pre > 0, pre, pre * s)
     mag = abs(k) * f2.abs() + abs(g_) * (amag * sc.abs() + sh.abs())
-    slack = C_SPLIT * abs(g_) * sc.abs() * amag if mode in ("bf16x3", "fp16x3") else torch.zeros_like(mag)
-    return k * f2 + g_ * y, mag, n_acc_for(K, 16 if mode == "lp16" else 4) + 4, slack
+    n_acc = n_acc_for(K, 16 if mode == "lp16" else 4) + 4
+    if mode == "fp16x3":
+        import split16_ref as S16
+        r = S16.gemm_ref(p2, S16.pair_abs(p2), W.detach().cpu().float(), torch.zeros(W.shape[0]))
+        slack = abs(g_) * sc.abs() * r[3]
+    elif mode == "bf16x3":
+        slack = C_SPLIT * abs(g_) * sc.abs() * amag
+    else:
+        slack = torch.zeros_like(mag)
+    return k * f2 + g_ * y, mag, n_acc, slack
 
 
 # ---- attention tail, clip pooling ----------------------------------------------------------------------------------------------
