@@ -378,7 +378,55 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const float* __restrict_
     out[(size_t)t * D + c] = mode ? acc : acc / (float)n;
 }
 
+// The same over SEGMENTS of the rows: tracklet t owns rows offsets[t] .. offsets[t+1]-1 (a ragged dense batch). thread -> one channel
+// of one tracklet; the arithmetic is clip_pool_kernel's, statement for statement (first clip, then eight loads in flight, ascending;
+// one division by the length), so every segment comes out bit-identical to clip_pool_kernel on that segment alone. Row indices are
+// clamped to [0, N]: whatever offsets holds, nothing outside feats is read; a segment empty after clamping yields NaN. Every value read
+// is also range-checked: a thread that saw an inf / NaN stores 1 to *nonfinite (all writers store the same word: no atomic).
+__global__ __launch_bounds__(256) void clip_pool_ragged_kernel(const float* __restrict__ feats, const int* __restrict__ offsets,
+                                                               float* __restrict__ out, int* __restrict__ nonfinite, int N, int D,
+                                                               int mode) {
+    const int t = blockIdx.x;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= D) return;
+    const int lo = min(max(offsets[t], 0), N), hi = min(max(offsets[t + 1], 0), N);
+    const int n = hi - lo;
+    if (n <= 0) {
+        out[(size_t)t * D + c] = __builtin_nanf("");
+        return;
+    }
+    const float* src = feats + (size_t)lo * D + c;
+    float acc = src[0];
+    bool bad = !(fabsf(acc) <= 3.402823466e+38f);
+    for (int i0 = 1; i0 < n; i0 += 8) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = i0 + i < n ? src[(size_t)(i0 + i) * D] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (i0 + i < n) {
+                bad |= !(fabsf(v[i]) <= 3.402823466e+38f);
+                if (mode) acc = (v[i] > acc || v[i] != v[i]) ? v[i] : acc;   // clip_pool_kernel's rule: first of equal maxima, NaN stays
+                else acc = acc + v[i];
+            }
+    }
+    out[(size_t)t * D + c] = mode ? acc : acc / (float)n;
+    if (bad && nonfinite) *nonfinite = 1;
+}
+
 }  // namespace
+
+extern "C" int agrl_clip_pool_ragged(const float* feats, const int* offsets, float* out, int* nonfinite, int N, int T, int D, int mode,
+                                     agrl_stream_t stream) {
+    AGRL_CHECK_ARG(feats && offsets && out, "agrl_clip_pool_ragged: null pointer");
+    AGRL_CHECK_ARG(N > 0 && T > 0 && D > 0, "agrl_clip_pool_ragged: bad shape N=%d T=%d D=%d", N, T, D);
+    AGRL_CHECK_ARG(mode == 0 || mode == 1, "agrl_clip_pool_ragged: mode must be 0 (mean) or 1 (max), got %d", mode);
+    AGRL_CHECK_ARG(cdiv(D, 256) <= 65535, "agrl_clip_pool_ragged: D=%d exceeds the grid", D);
+    hipLaunchKernelGGL(clip_pool_ragged_kernel, dim3(T, cdiv(D, 256)), dim3(256), 0, (hipStream_t)stream, feats, offsets, out, nonfinite,
+                       N, D, mode);
+    AGRL_CHECK_LAUNCH("agrl_clip_pool_ragged");
+    return 0;
+}
 
 extern "C" int agrl_clip_pool(const float* feats, float* out, int T, int n, int D, int mode, agrl_stream_t stream) {
     AGRL_CHECK_ARG(feats && out && T > 0 && n > 0 && D > 0, "agrl_clip_pool: bad arguments");

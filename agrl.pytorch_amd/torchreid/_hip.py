@@ -96,6 +96,7 @@ SIGNATURES = {
     "agrl_linear_nobias": [_p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_part_pool": [_p, _p, _p, _p, _p, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _p],
     "agrl_clip_pool": [_p, _p, _i, _i, _i, _i, _p],
+    "agrl_clip_pool_ragged": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "agrl_graph_gram": [_p, _p, _i, _i, _i, _i, _p],
     "agrl_graph_pair_product": [_p, _p, _p, _p, _i, _i, _i, _p],
     "agrl_graph_finalize": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p],

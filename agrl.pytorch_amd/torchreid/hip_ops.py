@@ -1348,6 +1348,47 @@ def clip_pool(feats, num_clips, mode="avg"):
     return out
 
 
+def ragged_offsets(offsets, rows):
+    """Validate the segment offsets of ``clip_pool_ragged`` against ``rows`` feature rows -> contiguous int32 ndarray (T+1,): a HOST
+    integer vector, strictly increasing, 0 <= offsets[0], offsets[T] <= rows. ValueError otherwise (a device tensor included)."""
+    if isinstance(offsets, torch.Tensor):
+        if offsets.is_cuda:
+            raise ValueError("clip_pool_ragged: offsets is a host array (it is validated before the upload)")
+        offsets = offsets.numpy()
+    o = np.asarray(offsets)
+    if o.ndim != 1 or o.size < 2 or o.dtype.kind not in "iu":
+        raise ValueError("clip_pool_ragged: offsets is an integer vector of T + 1 >= 2 entries, got %s %s" % (o.dtype, o.shape))
+    o = o.astype(np.int64)
+    if o[0] < 0 or o[-1] > rows or not bool((np.diff(o) > 0).all()):
+        raise ValueError("clip_pool_ragged: offsets must be strictly increasing within [0, %d], got %s%s" % (
+            rows, o[:8].tolist(), " ..." if o.size > 8 else ""))
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
+def clip_pool_ragged(feats, offsets, mode="avg", nonfinite=None):
+    """(N, D) fp32 clip embeddings + HOST offsets (T+1,) -> (T, D): mean / max over rows offsets[t] .. offsets[t+1]-1, every segment
+    bit-identical to ``clip_pool`` on it alone (agrl_clip_pool_ragged). ``offsets`` is validated here (``ragged_offsets``) and
+    uploaded non-blocking. ``nonfinite``: None or an int32 [1] tensor on the device, set to 1 when a value read is inf / NaN and never
+    cleared. One launch, no synchronisation."""
+    if not isinstance(feats, torch.Tensor) or feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_cuda:
+        raise ValueError("clip_pool_ragged: feats are fp32 (N, D) on the GPU")
+    if mode not in ("avg", "max"):
+        raise ValueError("clip_pool_ragged: mode is 'avg' or 'max', got %r" % (mode,))
+    N, D = feats.shape
+    off = ragged_offsets(offsets, N)
+    if D < 1:
+        raise ValueError("clip_pool_ragged: D = 0")
+    if nonfinite is not None and (nonfinite.dtype != torch.int32 or nonfinite.numel() != 1 or nonfinite.device != feats.device):
+        raise ValueError("clip_pool_ragged: nonfinite is an int32 [1] tensor on %s" % (feats.device,))
+    feats = feats.contiguous()
+    T = off.size - 1
+    out = torch.empty((T, D), dtype=torch.float32, device=feats.device)
+    off_d = torch.from_numpy(off).pin_memory().to(feats.device, non_blocking=True)
+    with _dev(feats):
+        call("agrl_clip_pool_ragged", ptr(feats), ptr(off_d), ptr(out), ptr(nonfinite), N, T, D, 0 if mode == "avg" else 1, _stream(feats))
+    return out
+
+
 def row_sqnorm(x):
     R, Cc = x.shape
     out = torch.empty((R,), dtype=torch.float32, device=x.device)

@@ -527,6 +527,16 @@ int agrl_attn_tail(const float* nodes, const float* gsum, const float* g_scale, 
  * in ascending order and divides once. */
 int agrl_clip_pool(const float* feats, float* out, int T, int n, int D, int mode, agrl_stream_t stream);
 
+/* The same for a RAGGED batch -- tracklets of different clip counts packed into one model batch (torchreid/evaluation.py,
+ * extract_features_packed): feats fp32 (N, D); offsets device int32 (T+1), strictly increasing, 0 <= offsets[0], offsets[T] <= N;
+ * tracklet t owns rows offsets[t] .. offsets[t+1]-1 -> out fp32 (T, D). Rows outside [offsets[0], offsets[T]) are not read. Every
+ * segment is bit-identical to agrl_clip_pool on that segment alone (T = 1, n = its length), in both modes. Row indices are clamped to
+ * [0, N], so no offsets content reads outside feats; a segment empty after clamping yields NaN.
+ *   nonfinite: NULL or device int32 [1]: set to 1 if any value read is inf or NaN, never set to 0 (the caller zeroes it once and
+ *   reads it once, after many calls). Any D >= 1, any segment length >= 1. */
+int agrl_clip_pool_ragged(const float* feats, const int* offsets, float* out, int* nonfinite, int N, int T, int D, int mode,
+                          agrl_stream_t stream);
+
 /* ---- tails of the STA baselines (sibling models sta / simple_sta) ---------------------------------------- */
 
 /* One pass over a layer-4 map (16-byte loads along C) for STA's spatial attention, torchreid/models/sta.py:213-222:
