@@ -80,6 +80,8 @@ SIGNATURES = {
     "agrl_bottleneck_seam_packed_bytes": [_i, _i, _i],   # returns long long (restype patched after loading)
     "agrl_bottleneck_seam_pack": [_p, _p, _p, _i, _i, _i, _p],
     "agrl_bottleneck_seam": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "agrl_bottleneck_chain_enabled": [_i],   # returns 0 / 1, not a status
+    "agrl_bottleneck_chain": [_p, _p, _p, _p, _p, _i, _i, _p],
     "agrl_conv3x3_packed_bytes": [_i, _i],               # returns long long
     "agrl_conv1x1_packed_bytes": [_i, _i],               # returns long long
     "agrl_conv1x1_pack": [_p, _p, _i, _i, _p],

@@ -768,6 +768,62 @@ def bottleneck_seam(y2, packed, b3, residual, b1_next, dims):
     return out, z
 
 
+CHAIN_MAX = 4   # Bottlenecks per agrl_bottleneck_chain launch
+
+
+def bottleneck_chain_table(blocks):
+    """The device table of agrl_bottleneck_chain for the consecutive Bottlenecks ``blocks`` (pack_stage dicts with 'c2p' and 'seam';
+    blocks[i]['seam'] already holds the conv1 of the block behind it): one row of 8 pointers per block -- conv2's packed stream, b2,
+    the seam's packed stream, b3, the next conv1's bias ('seam_b1n'). Built once per pack: the tensors it points into are the pack's."""
+    rows = [[b['c2p'].data_ptr(), b['c2'][1].data_ptr(), b['seam'].data_ptr(), b['c3'][1].data_ptr(), b['seam_b1n'].data_ptr(), 0, 0, 0]
+            for b in blocks]
+    return torch.tensor(rows, dtype=torch.int64).to(blocks[0]['c2p'].device)
+
+
+def bottleneck_chain_block_ok(blk):
+    """A pack_stage block the chained kernel can run: packed 3x3 and seam of the 256 / 1024 / 256 shape, identity shortcut."""
+    return ('c2p' in blk and 'seam' in blk and 'seam_b1n' in blk and blk['ds'] is None and blk['stride'] == 1
+            and blk.get('seam_dims') == (256, 1024, 256) and tuple(blk['c2'][0].shape) == (256, 3, 3, 256)
+            and blk['c2'][0].dtype == LP_DTYPE)
+
+
+def bottleneck_chain_supported(z, a, blocks, forced=False):
+    """agrl_bottleneck_chain applies: the 16-bit type, contiguous (F,16,8,256) / (F,16,8,1024) maps, 1 .. CHAIN_MAX blocks that are
+    all bottleneck_chain_block_ok -- and the library's switch says so for this many frames (``forced``: the switch is not asked)."""
+    if not (1 <= len(blocks) <= CHAIN_MAX and all(bottleneck_chain_block_ok(b) for b in blocks)):
+        return False
+    if not (z.dtype == LP_DTYPE and a.dtype == LP_DTYPE and z.dim() == 4 and tuple(z.shape[1:]) == (16, 8, 256)
+            and tuple(a.shape) == (z.shape[0], 16, 8, 1024) and z.is_contiguous() and a.is_contiguous()):
+        return False
+    return forced or bool(_hip.lib().agrl_bottleneck_chain_enabled(int(z.shape[0])))
+
+
+def bottleneck_chain(z, a, table, n, work=None, out=None):
+    """``n`` chained Bottlenecks of layer 3 in one launch (csrc/bottleneck_chain.hip): z (F,16,8,256) conv1 output of the first, a
+    (F,16,8,1024) the residual entering it, ``table`` from bottleneck_chain_table (rows 0 .. n-1 are used). ``work``: n - 1 buffers
+    like ``a`` for the inner residual-stream maps, reusable from call to call (None: allocated here); ``out``: the buffer of a_n. No two
+    of a, work[i], out may overlap (the library checks).
+    -> (a_n, z_{n+1}): the last block's output and the conv1 output of the block behind the chain."""
+    F = z.shape[0]
+    assert 1 <= n <= CHAIN_MAX and table.dtype == torch.int64 and tuple(table.shape[1:]) == (8,) and table.shape[0] >= n
+    assert z.dtype == LP_DTYPE and a.dtype == LP_DTYPE and tuple(z.shape) == (F, 16, 8, 256) and tuple(a.shape) == (F, 16, 8, 1024)
+    assert z.is_contiguous() and a.is_contiguous()
+    if work is None:
+        work = [torch.empty_like(a) for _ in range(n - 1)]
+    assert len(work) >= n - 1 and all(w.dtype == a.dtype and w.numel() == a.numel() and w.is_contiguous() for w in work[:n - 1])
+    out = torch.empty_like(a) if out is None else out
+    assert out.dtype == a.dtype and out.numel() == a.numel() and out.is_contiguous()
+    zn = torch.empty_like(z)
+    bufs = (C.c_void_p * n)(*([ptr(w) for w in work[:n - 1]] + [ptr(out)]))
+    if _hip.PROFILE is not None:
+        M = F * 128
+        _hip.PROFILE_TAG = {"flops": 2.0 * M * n * (9 * 256 * 256 + 2 * 256 * 1024),
+                            "bytes": 2.0 * (z.numel() + zn.numel() + (2 * n) * a.numel()) + n * 2.0 * (9 * 256 * 256 + 2 * 256 * 1024)}
+    with _dev(z):
+        call("agrl_bottleneck_chain", ptr(z), ptr(a), ptr(table), bufs, ptr(zn), F, n, _stream(z))
+    return out, zn
+
+
 def conv3x3_packed_enabled():
     """Always True: the models run every packed 3x3 weight through conv3x3_packed. Kept for bench.py's labels."""
     return True

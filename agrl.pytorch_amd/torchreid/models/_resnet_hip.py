@@ -146,7 +146,24 @@ def pack_stage(stage, dtype, seam=False, split16=False):
             if ops.bottleneck_seam_supported(blk['c3'][0], nxt['c1'][0]):
                 blk['seam'] = ops.bottleneck_seam_pack(blk['c3'][0], nxt['c1'][0])
                 blk['seam_dims'] = (blk['c3'][0].shape[3], blk['c3'][0].shape[0], nxt['c1'][0].shape[0])
+                blk['seam_b1n'] = nxt['c1'][1]
+        # runs of consecutive blocks that one ops.bottleneck_chain launch can take (layer 3's blocks 1-4): the first block of a run
+        # carries the run's device table of per-block pointers, built here once (it lives and dies with the pack)
+        i = 0
+        while i < len(blocks):
+            run = chain_run(blocks, i)
+            if run:
+                blocks[i]['chain'] = (run, ops.bottleneck_chain_table(blocks[i:i + run]))
+            i += max(run, 1)
     return blocks
+
+
+def chain_run(blocks, i):
+    """Length of the run of consecutive blocks from ``i`` on that ops.bottleneck_chain can take in one launch (0: none)."""
+    n = 0
+    while i + n < len(blocks) and n < ops.CHAIN_MAX and ops.bottleneck_chain_block_ok(blocks[i + n]):
+        n += 1
+    return n
 
 
 def pack_planes(blk):
@@ -301,12 +318,23 @@ def run_trunk(a, blocks):
     """layer1..layer3 Bottlenecks. Where the fused kernel exists (layer 1, bf16) the last conv of block i also
     produces the first conv of block i+1 from the tile it still holds in LDS (ops.bottleneck_tail)."""
     z = None  # conv1 output of the current block, when the previous block's tail already computed it
+    skip = 0  # blocks a chain launch has already run
     for i, blk in enumerate(blocks):
+        if skip:
+            skip -= 1
+            continue
         if is_inloop(blk):
             a = run_block_inloop(a, blk)
             continue
         nxt = blocks[i + 1] if i + 1 < len(blocks) else None
         y = z if z is not None else ops.conv_bn_act(a, blk['c1'][0], blk['c1'][1], 1, 0, True)
+        if 'chain' in blk and ops.bottleneck_chain_supported(y, a, blocks[i:i + blk['chain'][0]]):
+            # layer 3's blocks 1-4: 3x3 + conv3 + residual + next conv1 of the whole run in ONE launch, a frame per workgroup
+            # (ops.bottleneck_chain); z is then the conv1 output of the block behind the run
+            n, table = blk['chain']
+            a, z = ops.bottleneck_chain(y, a, table, n)
+            skip = n - 1
+            continue
         if nxt is not None:
             # layer 1: 3x3 + conv3 (+ shortcut) + next conv1 in ONE pass over 8 x 8 pixel tiles (ops.bottleneck_block)
             ds = None if blk['ds'] is None else (blk['ds'][0], blk['ds_stride'])

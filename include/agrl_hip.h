@@ -273,6 +273,22 @@ int agrl_bottleneck_seam_pack(const void* w3, const void* w1_next, void* packed,
 int agrl_bottleneck_seam(const void* y2, const void* packed, const float* b3, const void* residual, void* out,
                          const float* b1_next, void* z, int M, int Cmid, int Cout, int Cnext, agrl_stream_t stream);
 
+/* The stride-1 middle of layer 3 as one kernel per frame (16-bit build type only): n = 1 .. 4 consecutive Bottlenecks with
+ * 256 / 1024 / 256 channels on 16 x 8 maps, every workgroup owning one frame (vmgn.py:52-64 of block i + :48-50 of block i + 1):
+ *   y_i = relu(conv3x3_i(z_i) + b2_i);  a_i = relu(conv3_i(y_i) + b3_i + a_{i-1});  z_{i+1} = relu(conv1_{i+1}(a_i) + b1_{i+1})
+ * y_i and the inner z_i never leave the LDS. Bit-identical to agrl_conv3x3_packed_bn_act + agrl_bottleneck_seam applied n times.
+ *   z1 (frames,16,8,256) conv1 output of the first block, a0 (frames,16,8,1024) the residual entering it;
+ *   table: DEVICE array of n rows of 8 pointers {agrl_conv3x3_pack of conv2, b2, agrl_bottleneck_seam_pack of (conv3, next conv1),
+ *          b3, b1_next, 0, 0, 0};
+ *   a_out: HOST array of n device pointers, a_out[i] (frames,16,8,1024) receives a_{i+1}: a_out[n-1] is the result, the others are
+ *          workspace. The n + 1 residual-stream buffers must not overlap one another;
+ *   z_out (frames,16,8,256) receives z_{n+1}.
+ * agrl_bottleneck_chain_enabled(frames): 1 where the models should take this route for that many frames (AGRL_L3_CHAIN = 1 / 0
+ * forces it on / off), else 0. */
+int agrl_bottleneck_chain_enabled(int frames);
+int agrl_bottleneck_chain(const void* z1, const void* a0, const void* table, void* const* a_out, void* z_out, int frames, int n,
+                          agrl_stream_t stream);
+
 /* The 3x3 conv of a layer-3 / layer-4 Bottleneck (torchreid/models/vmgn.py:52-54: conv2 / bn2 / relu, stride 1, pad 1) with its
  * static weights re-ordered ONCE into per-wave MFMA fragment streams (16-bit build type only):
  *   out (N,H,W,Cout) = act(conv3x3(x (N,H,W,Cin), w (Cout,3,3,Cin) OHWI) + bias)
