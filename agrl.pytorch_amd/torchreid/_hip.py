@@ -66,6 +66,7 @@ SIGNATURES = {
     "agrl_stem_conv_bn_relu_maxpool_lp16_u8": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p],
     "agrl_stem_split16_u8": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "agrl_frames_normalize_u8": [_p, _p, _i, _p, _i, _i, _i, _p],
+    "agrl_frames_normalize_erase_u8": [_p, _p, _i, _p, _p, _i, _f, _f, _f, _p, _i, _i, _i, _p],
     "agrl_clip_resample_u8": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
     "agrl_resample_taps_u8": [_i, _i, _p, _p, _p],
     "agrl_split16_planes": [_p, _p, C.c_longlong, _i, _i, _p],

@@ -17,11 +17,20 @@ agrl_frames_normalize_u8.
     GroupRandomCrop(crop_size)                a crop_size window at one random offset inside the (misaligned) frame
     GroupRandomHorizontalFlip(p)              the flip bit
 
-Random erasing (GroupRandomErasing) is OUT OF SCOPE: the reference applies it after Normalize and writes the raw channel mean into
-the normalised tensor -- a value no uint8 pixel maps to, so it cannot be expressed on a uint8 clip; it stays an operation on the
-normalised fp32 tensor.
+Random erasing (GroupRandomErasing, --rand-erase) is the one operation of transform_train that is not a geometry of the uint8 clip: the
+reference applies it after Normalize and writes the raw channel mean into the normalised tensor -- a value no uint8 pixel maps to. It
+rides in the pass that makes the fp32 tensor instead: ``erase_geometry`` draws the reference's rectangles per frame on the host (all
+fitting ones of its 100 attempts: its loop never returns), and ``hip_ops.frames_normalize_erase`` (agrl_frames_normalize_erase_u8)
+normalises the resampled clip and erases in one launch. ``DeviceClipTransform(..., train=True, rand_erase=True)`` therefore returns the
+normalised fp32 clip the train step takes, not a uint8 one. The host still produces geometry only, never pixels.
+
+OUT OF SCOPE: one rectangle shared by the frames of a clip (the reference draws per frame), the reference's unused
+GroupRandom2DTranslation, ElasticTransform and RandomPoseAugmentation, and JPEG decode.
 """
 from __future__ import annotations
+
+import math
+import random
 
 import numpy as np
 import torch
@@ -102,21 +111,96 @@ def train_geometry(sizes, rng, misalign=False, rand_crop=False, flip=False, crop
         np.zeros((0, s.shape[1], 8), dtype=np.int32)
 
 
+ERASE_ATTEMPTS = 100   # the reference's loop (transforms.py:298, 511)
+
+
+def _erase_frame(height, width, uniform, randint, probability, sl, sh, r1, first):
+    """One frame's rectangles [(y, x, h, w), ...], draw for draw GroupRandomErasing._instance_process (``first``: RandomErasing.__call__,
+    which returns at the first attempt that fits). ``uniform(a, b)`` / ``randint(a, b)`` (both ends included) are the random module's."""
+    rects = []
+    if uniform(0, 1) > probability:
+        return rects
+    for _ in range(ERASE_ATTEMPTS):
+        target_area = uniform(sl, sh) * (height * width)
+        aspect = uniform(r1, 1 / r1)
+        h = int(round(math.sqrt(target_area * aspect)))   # Python's round: half to even
+        w = int(round(math.sqrt(target_area / aspect)))
+        if w < width and h < height:
+            y = randint(0, height - h)
+            x = randint(0, width - w)
+            rects.append((y, x, h, w))   # h or w may be 0 (a frame one pixel high): drawn, erases nothing
+            if first:
+                break
+    return rects
+
+
+def erase_geometry(shape, height, width, rng, probability=0.5, sl=0.02, sh=0.4, r1=0.3, attempts='all'):
+    """Random erasing as geometry: the rectangles the reference erases in ``shape`` (an int or a tuple, e.g. (B, S)) frames of
+    height x width, drawn PER FRAME in C order -> (rects int32 (*shape, R, 4) of rows (y, x, h, w), zero behind each frame's rows;
+    counts int32 (*shape)), R = the largest count (at least 1). Per frame: u = uniform(0, 1), nothing when u > probability; else 100
+    attempts of area = uniform(sl, sh) H W, aspect = uniform(r1, 1 / r1), h = int(round(sqrt(area aspect))), w = int(round(sqrt(area /
+    aspect))) and, where h < H and w < W, y = randint(0, H - h), x = randint(0, W - w). ``attempts='all'`` keeps every attempt that fits,
+    as GroupRandomErasing does (transforms.py:293-321: its loop never returns; up to 100 rectangles, a 256x128 frame ends ~96 % covered);
+    ``'first'`` stops at the first, as RandomErasing (transforms.py:506-531). ``rng``: a ``random.Random`` -- draw for draw the
+    reference's stream: seeded like the random module it yields the reference's rectangles -- or a numpy Generator / a seed (the same
+    rule on rng.uniform / rng.integers, as ``train_geometry`` samples)."""
+    if attempts not in ('all', 'first'):
+        raise ValueError("erase_geometry: attempts is 'all' (GroupRandomErasing) or 'first' (RandomErasing), got %r" % (attempts,))
+    shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(v) for v in shape)
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError("erase_geometry: frames of %d x %d" % (height, width))
+    if isinstance(rng, random.Random):
+        uniform, randint = rng.uniform, rng.randint
+    else:
+        if not isinstance(rng, np.random.Generator):
+            rng = np.random.default_rng(rng)
+        uniform, randint = (lambda a, b: float(rng.uniform(a, b))), (lambda a, b: int(rng.integers(a, b + 1)))
+    frames = [_erase_frame(height, width, uniform, randint, probability, sl, sh, r1, attempts == 'first')
+              for _ in range(int(np.prod(shape, dtype=np.int64)))]
+    counts = np.array([len(f) for f in frames], dtype=np.int32).reshape(shape)
+    rects = np.zeros((len(frames), max([len(f) for f in frames] + [1]), 4), dtype=np.int32)
+    for n, f in enumerate(frames):
+        if f:
+            rects[n, :len(f)] = f
+    return rects.reshape(shape + rects.shape[1:]), counts
+
+
+GEOMETRY_FLAGS = ("misalign", "rand_crop", "flip", "crop_size", "misalign_ratio", "p")
+ERASE_FLAGS = ("probability", "sl", "sh", "r1", "attempts", "value")
+
+
 class DeviceClipTransform:
     """``DeviceClipTransform(height, width, train=False, **flags)(clips, sizes=None)``: uint8 (B,S,Hs,Ws,3) clips on the GPU -> uint8
     (B,S,height,width,3), ready for ``model(x, adj)`` or the train step. ``sizes``: int (B,S,2) valid extents (height, width) of the
     frames inside the padded container, default the container's size. ``train=False`` is transform_test (resize); ``train=True`` takes
     the flags of ``train_geometry`` (misalign, rand_crop, flip, crop_size, misalign_ratio, p) and ``rng`` (a numpy Generator or a seed).
-    The geometry of the last call is kept in ``last_geometry`` (host int32 (B,S,8))."""
+    The geometry of the last call is kept in ``last_geometry`` (host int32 (B,S,8)).
+
+    ``rand_erase=True`` (train only) adds the reference's random erasing, which works on the normalised tensor: the call then returns
+    the NORMALISED fp32 (B,S,3,height,width) clip the train step takes -- the resample, then ``hip_ops.frames_normalize_erase``: two
+    launches. ``erase``: a dict of ``erase_geometry``'s keyword arguments (probability, sl, sh, r1, attempts) plus ``value`` (what is
+    written, default hip_ops.PIXEL_MEAN as the driver's GroupRandomErasing()); ``pixel_mean`` / ``pixel_std``: the normalisation. The
+    rectangles are drawn from ``rng`` after the clip geometry and kept in ``last_erase`` (host (rects (B,S,R,4), counts (B,S)))."""
 
     def __init__(self, height, width, train=False, rng=None, **flags):
         self.height, self.width, self.train = int(height), int(width), bool(train)
-        unknown = set(flags) - {"misalign", "rand_crop", "flip", "crop_size", "misalign_ratio", "p"}
+        unknown = set(flags) - set(GEOMETRY_FLAGS) - {"rand_erase", "erase", "pixel_mean", "pixel_std"}
         if unknown or (flags and not train):
             raise TypeError("DeviceClipTransform: unexpected arguments %s" % sorted(unknown or flags))
-        self.flags = flags
+        self.flags = {k: v for k, v in flags.items() if k in GEOMETRY_FLAGS}
+        self.rand_erase = bool(flags.get("rand_erase", False))
+        erase = flags.get("erase")
+        if not self.rand_erase and set(flags) & {"erase", "pixel_mean", "pixel_std"}:
+            raise TypeError("DeviceClipTransform: erase, pixel_mean and pixel_std go with rand_erase=True")
+        if erase is not None and (not isinstance(erase, dict) or set(erase) - set(ERASE_FLAGS)):
+            raise TypeError("DeviceClipTransform: erase is a dict with keys from %s, got %r" % (ERASE_FLAGS, erase))
+        self.erase = {k: v for k, v in (erase or {}).items() if k != "value"}
+        self.pixel_mean, self.pixel_std = flags.get("pixel_mean", ops.PIXEL_MEAN), flags.get("pixel_std", ops.PIXEL_STD)
+        self.erase_value = (erase or {}).get("value", ops.PIXEL_MEAN)
         self.rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
         self.last_geometry = None
+        self.last_erase = None
 
     def geometry(self, sizes):
         return train_geometry(sizes, self.rng, **self.flags) if self.train else eval_geometry(sizes)
@@ -133,4 +217,9 @@ class DeviceClipTransform:
             raise ValueError("sizes is (B,S,2) = %s, got %s" % ((B, S, 2), sizes.shape))
         self.last_geometry = self.geometry(sizes)
         out = ops.clip_resample(clips.contiguous().view(B * S, Hs, Ws, 3), self.last_geometry.reshape(B * S, 8), (self.height, self.width))
-        return out.view(B, S, self.height, self.width, 3)
+        if not self.rand_erase:
+            return out.view(B, S, self.height, self.width, 3)
+        rects, counts = self.last_erase = erase_geometry((B, S), self.height, self.width, self.rng, **self.erase)
+        out = ops.frames_normalize_erase(out, rects.reshape((B * S,) + rects.shape[2:]), counts.reshape(B * S), self.erase_value,
+                                         self.pixel_mean, self.pixel_std)
+        return out.view(B, S, 3, self.height, self.width)

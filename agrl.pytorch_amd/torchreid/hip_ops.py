@@ -139,6 +139,88 @@ def frames_normalize(u8, mean=PIXEL_MEAN, std=PIXEL_STD):
     return out
 
 
+def erase_lists(rects, counts, N, H, W):
+    """Validate per-frame erase rectangles against N frames of H x W -> (rects int32 ndarray (N, R, 4), counts int32 ndarray (N,)).
+    ``rects`` HOST integer (N, R, 4), rows (y, x, h, w) = image rows y .. y+h-1, columns x .. x+w-1; ``counts`` HOST integer (N,): the
+    first counts[n] rows of frame n count, whatever stands behind them is ignored. ValueError naming the first offending frame: device
+    arrays, a wrong shape, R above ERASE_MAX_RECTS, a count outside 0..R, a negative entry or a rectangle that leaves the frame."""
+    for a in (rects, counts):
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            raise ValueError("frames_normalize_erase: rects and counts are host arrays (they are validated before the upload)")
+    r = np.asarray(rects)
+    c = np.asarray(counts)
+    if r.dtype.kind not in "iu" or c.dtype.kind not in "iu" or r.ndim != 3 or r.shape[0] != N or r.shape[2] != 4 or c.shape != (N,):
+        raise ValueError("frames_normalize_erase: rects is an integer (N, R, 4) array and counts an integer (N,) array with N = %d, got %s %s "
+                         "and %s %s" % (N, r.dtype, r.shape, c.dtype, c.shape))
+    R = r.shape[1]
+    if R > ERASE_MAX_RECTS:
+        raise ValueError("frames_normalize_erase: %d rectangles per frame, at most %d" % (R, ERASE_MAX_RECTS))
+    r, c = np.ascontiguousarray(r, dtype=np.int64), np.ascontiguousarray(c, dtype=np.int64)
+    if ((c < 0) | (c > R)).any():
+        n = int(np.argmax((c < 0) | (c > R)))
+        raise ValueError("frames_normalize_erase: frame %d has a count of %d, 0..%d" % (n, int(c[n]), R))
+    live = np.arange(R)[None, :] < c[:, None]
+    bad = live & ((r < 0).any(2) | (np.abs(r) >= 2 ** 30).any(2) | (r[..., 0] + r[..., 2] > H) | (r[..., 1] + r[..., 3] > W))
+    if bad.any():
+        n, i = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError("frames_normalize_erase: frame %d has rectangle %d = (y %d, x %d, h %d, w %d) outside its %d x %d frame" % (
+            (n, i) + tuple(int(v) for v in r[n, i]) + (H, W)))
+    return r.astype(np.int32), c.astype(np.int32)
+
+
+def _erase_value(value):
+    v = torch.tensor([float(f) for f in value], dtype=torch.float32)
+    if v.numel() != 3:
+        raise ValueError("the erase value is three numbers, one per channel: got %r" % (value,))
+    return v
+
+
+def frames_normalize_erase_reference(u8, rects, counts, value=PIXEL_MEAN, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """``frames_normalize_reference`` followed by the reference's random erasing (GroupRandomErasing / RandomErasing, transforms.py:274-324,
+    487-531) as slice assignment: out[n, c, y:y+h, x:x+w] = float32(value[c]) for the first counts[n] rows (y, x, h, w) of rects[n]. uint8
+    frames (..., 3, H, W) or (..., H, W, 3) with rects (..., R, 4) and counts (...) -> fp32 (..., 3, H, W). Pure torch, any device: what
+    the CPU path uses and agrl_frames_normalize_erase_u8 is compared with bit for bit."""
+    out = frames_normalize_reference(u8, mean, std)
+    H, W = out.shape[-2:]
+    flat = out.view(-1, 3, H, W)
+    r = np.asarray(rects)
+    r, c = erase_lists(r.reshape((-1,) + tuple(r.shape[-2:])), np.asarray(counts).reshape(-1), flat.shape[0], H, W)
+    fill = _erase_value(value).to(out.device)
+    for n in range(flat.shape[0]):
+        for y, x, h, w in r[n, :c[n]].tolist():
+            flat[n, :, y:y + h, x:x + w] = fill.view(3, 1, 1)
+    return out
+
+
+def frames_normalize_erase(u8, rects, counts, value=PIXEL_MEAN, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """The same on the GPU (agrl_frames_normalize_erase_u8): uint8 frames (N,3,H,W) or (N,H,W,3) on the device; ``rects`` / ``counts``
+    HOST integer arrays (N, R, 4) / (N,), validated here (``erase_lists``) and uploaded non-blocking from pinned memory, in one copy
+    -> fp32 NCHW (N,3,H,W). One launch, no synchronisation."""
+    if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise ValueError("frames_normalize_erase: frames are uint8 (N,3,H,W) or (N,H,W,3), got %s" % (
+            "%s %s" % (u8.dtype, tuple(u8.shape)) if isinstance(u8, torch.Tensor) else type(u8),))
+    nchw = frames_layout(u8.shape) == 'nchw'
+    r, c = erase_lists(rects, counts, u8.shape[0], u8.shape[2 if nchw else 1], u8.shape[3 if nchw else 2])
+    fill = [float(f) for f in _erase_value(value)]
+    if not u8.is_cuda:
+        raise ValueError("frames_normalize_erase: frames must be on the GPU (frames_normalize_erase_reference is the CPU form)")
+    x, table, layout, N, H, W = _u8_frames(u8, mean, std)
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=x.device)
+    if N == 0:
+        return out
+    R = r.shape[1]
+    rects_d = counts_d = None
+    if R > 0:
+        lists = torch.from_numpy(np.concatenate([r.reshape(-1), c])).pin_memory().to(x.device, non_blocking=True)
+        rects_d, counts_d = lists[:N * R * 4], lists[N * R * 4:]
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * x.numel() + 4.0 * out.numel()}
+    with _dev(x):
+        call("agrl_frames_normalize_erase_u8", ptr(x), ptr(table), layout, ptr(rects_d), ptr(counts_d), R, fill[0], fill[1], fill[2],
+             ptr(out), N, H, W, _stream(x))
+    return out
+
+
 def clip_frames(x):
     """Validate uint8 clips as the models take them -- (B,S,3,H,W) or (B,S,H,W,3) -> (layout, B, S, H, W); ValueError otherwise."""
     if x.dim() != 5:
@@ -148,10 +230,22 @@ def clip_frames(x):
     return layout, x.shape[0], x.shape[1], H, W
 
 
-def clips_to_float(x, mean=PIXEL_MEAN, std=PIXEL_STD):
+def clips_to_float(x, mean=PIXEL_MEAN, std=PIXEL_STD, erase=None):
     """uint8 clips (B,S,3,H,W) / (B,S,H,W,3) -> fp32 (B,S,3,H,W), normalised: agrl_frames_normalize_u8 on the GPU, the table on the CPU.
-    The models call this in front of every path that does not fuse the normalisation into the stem (training, CPU)."""
+    The models call this in front of every path that does not fuse the normalisation into the stem (training, CPU).
+    ``erase`` = (rects, counts[, value]), host integer (B,S,R,4) / (B,S): random erasing in the same pass (``frames_normalize_erase`` on
+    the GPU, ``frames_normalize_erase_reference`` on the CPU); value defaults to PIXEL_MEAN, what GroupRandomErasing writes."""
     _, B, S, H, W = clip_frames(x)
+    if erase is not None:
+        rects, counts = np.asarray(erase[0]), np.asarray(erase[1])
+        value = erase[2] if len(erase) > 2 else PIXEL_MEAN
+        if rects.ndim != 4 or rects.shape[:2] != (B, S) or counts.shape != (B, S):
+            raise ValueError("clips_to_float: erase is (rects (B,S,R,4), counts (B,S)) with (B,S) = %s, got %s and %s" % (
+                (B, S), rects.shape, counts.shape))
+        if not x.is_cuda:
+            return frames_normalize_erase_reference(x, rects, counts, value, mean, std)
+        return frames_normalize_erase(x.reshape((B * S,) + tuple(x.shape[2:])), rects.reshape((B * S,) + tuple(rects.shape[2:])),
+                                      counts.reshape(B * S), value, mean, std).view(B, S, 3, H, W)
     if x.is_cuda:
         return frames_normalize(x.reshape((B * S,) + tuple(x.shape[2:])), mean, std).view(B, S, 3, H, W)
     return frames_normalize_reference(x, mean, std)
@@ -162,6 +256,7 @@ RESAMPLE_TAPS = 17        # taps per output element the kernel holds: a downscal
 RESAMPLE_MAX_SCALE = 8
 RESAMPLE_MAX_OUT = 512
 _RESAMPLE_BITS = 22       # Pillow's PRECISION_BITS for 8-bit channels
+ERASE_MAX_RECTS = 128     # rectangles per frame agrl_frames_normalize_erase_u8 holds (the reference draws at most 100)
 
 
 @functools.lru_cache(maxsize=4096)

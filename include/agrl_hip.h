@@ -111,6 +111,19 @@ int agrl_stem_split16_u8(const unsigned char* x, const float* table, int layout,
 int agrl_frames_normalize_u8(const unsigned char* x, const float* table, int layout, float* out, int N, int H, int W,
                              agrl_stream_t stream);
 
+/* The same pass with the reference's random erasing in it (GroupRandomErasing / RandomErasing, transforms.py:274-324, 487-531, which run
+ * BEHIND Normalize and write a constant per channel into the normalised tensor): out[n][c][y][x] = fill_c where (y, x) lies in any of the
+ * first counts[n] rectangles of frame n, table[c][x_u8] elsewhere. x, table, layout, out, N, H, W as in agrl_frames_normalize_u8.
+ *   rects     : device int32 (N, max_rects, 4), rows (y, x, h, w): image rows y .. y+h-1, columns x .. x+w-1. h or w <= 0: nothing.
+ *               Frames have fewer than 2^29 pixels; the kernel cuts entries beyond +-2^29 to that before it compares
+ *   counts    : device int32 (N); clamped to 0..max_rects by the kernel. Rows behind counts[n] are never read
+ *   max_rects : 0..128. With 0, rects and counts may be NULL and the output is agrl_frames_normalize_u8's bit for bit
+ * The host samples the rectangles (geometry only, as for agrl_clip_resample_u8) and checks them against the frame; the kernel compares
+ * them with each pixel's own coordinates and forms no address from them, so it is memory-safe for any list contents. */
+int agrl_frames_normalize_erase_u8(const unsigned char* x, const float* table, int layout, const int* rects, const int* counts,
+                                   int max_rects, float fill0, float fill1, float fill2, float* out, int N, int H, int W,
+                                   agrl_stream_t stream);
+
 /* Resize / crop / flip of decoded frames in front of the stems: the Pillow half of the reference's transforms (GroupResize, and for
  * training GroupMisAlignAugment, GroupRandomCrop and GroupRandomHorizontalFlip, train_vidreid_xent_htri.py:192-217), BIT-EXACT with
  * Image.crop(window).resize((OW, OH), BILINEAR) followed by the left-right flip.
