@@ -69,6 +69,8 @@ SIGNATURES = {
     "agrl_frames_normalize_erase_u8": [_p, _p, _i, _p, _p, _i, _f, _f, _f, _p, _i, _i, _i, _p],
     "agrl_clip_resample_u8": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
     "agrl_resample_taps_u8": [_i, _i, _p, _p, _p],
+    "agrl_jpeg_decode_workspace": [_i],   # returns size_t
+    "agrl_jpeg_decode_u8": [_p, C.c_longlong, _p, _p, _i, _p, _i, _p, _i, _p, C.c_size_t, _p, _i, _i, _p, _i, _p],
     "agrl_split16_planes": [_p, _p, C.c_longlong, _i, _i, _p],
     "agrl_split16_weight_planes": [_p, _p, C.c_longlong, _i, _f, _p],
     "agrl_split16_weights_inloop": [_p, _p, C.c_longlong, _i, _p],
@@ -196,6 +198,7 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = _i
         h.agrl_re_ranking_workspace.restype = C.c_size_t
+        h.agrl_jpeg_decode_workspace.restype = C.c_size_t
         h.agrl_bn_workspace.restype = C.c_size_t
         h.agrl_col_sum_workspace.restype = C.c_size_t
         h.agrl_conv_wgrad_workspace.restype = C.c_size_t

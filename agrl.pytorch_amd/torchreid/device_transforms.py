@@ -25,7 +25,8 @@ normalises the resampled clip and erases in one launch. ``DeviceClipTransform(..
 normalised fp32 clip the train step takes, not a uint8 one. The host still produces geometry only, never pixels.
 
 OUT OF SCOPE: one rectangle shared by the frames of a clip (the reference draws per frame), the reference's unused
-GroupRandom2DTranslation, ElasticTransform and RandomPoseAugmentation, and JPEG decode.
+GroupRandom2DTranslation, ElasticTransform and RandomPoseAugmentation. (JPEG decode, the stage in front of this one, is
+torchreid/device_decode.py.)
 """
 from __future__ import annotations
 

@@ -69,6 +69,28 @@ def device_prefetch(batches, device):
         yield _claim(pending, main)
 
 
+def decode_batches(batches, device, decoder=None):
+    """Loader items whose ``imgs`` entry is a nested list of ENCODED frames -- JPEG ``bytes``, [b][S] or [b][n][S] -- decoded on the
+    device (``device_decode.DeviceJpegDecoder``: headers on the host, entropy decode / IDCT / upsampling / colour on the GPU, byte for
+    byte Pillow's ``Image.open().convert('RGB')``): yields the 5-tuples (imgs uint8 (b,[n,]S,Hmax,Wmax,3) on ``device``, pids, camids,
+    adj, sizes int (b,[n,]S,2)) that ``extract_features(..., frame_size=...)`` and ``extract_features_packed`` take, so
+    ``evaluate(..., clip_batch=32, frame_size=...)`` on JPEG files needs no other change. Items whose imgs is already a tensor pass through.
+    Files outside the decoder's subset take its Pillow fallback; ``decoder``: one to reuse (its counters run on)."""
+    from torchreid.device_decode import DeviceJpegDecoder, _nested
+    decoder = DeviceJpegDecoder(device) if decoder is None else decoder
+    for item in batches:
+        imgs, pid, camid, adj = item[:4]
+        if isinstance(imgs, torch.Tensor):
+            yield item
+            continue
+        flat, shape = _nested(imgs)
+        if len(shape) not in (2, 3):
+            raise ValueError("encoded imgs is a nested list [b][S] or [b][n][S] of bytes, got nesting %s" % (shape,))
+        clips, sizes = decoder.decode(flat, shape)
+        # the frames are on the device: the adjacency goes with them (the extractions take an item from one side or the other)
+        yield (clips, pid, camid, adj.to(device, non_blocking=True) if isinstance(adj, torch.Tensor) else adj, sizes)
+
+
 def _claim(pending, main):
     item, done = pending
     main.wait_event(done)
@@ -436,20 +458,21 @@ def match_and_rank(qf, q_pids, q_camids, gf, g_pids, g_camids, dist_metric="cosi
 
 @torch.no_grad()
 def evaluate(model, query_batches, gallery_batches, dist_metric="cosine", pool="avg", max_rank=50,
-             ranks=(1, 5, 10, 20), verbose=False, re_rank=False, clip_batch=None):
+             ranks=(1, 5, 10, 20), verbose=False, re_rank=False, clip_batch=None, frame_size=None):
     """Single-process form of the reference's ``test()``: returns (rank1, mAP) and, like the reference, can print the
     CMC table. This process extracts EVERY batch itself, so the gallery it ranks against is whole: all three stages run with
     ``local_only=True`` -- no collective anywhere, no rank offset -- and the call is safe on one rank of an initialised process
     group (``tests/test_parallel_gloo.py::test_rank0_only_evaluate``). For the sharded form every rank runs ``extract_features``
     on its slice and then ``match_and_rank`` (both collective by default).
     ``clip_batch``: an integer routes both extractions through ``extract_features_packed`` -- the dense protocols' ragged tracklets
-    packed into model batches of that many clips; None (the default) is ``extract_features``."""
+    packed into model batches of that many clips; None (the default) is ``extract_features``. ``frame_size``: handed to the
+    extraction, for decoded frames of any size (``decode_batches`` makes such batches out of JPEG bytes)."""
     if clip_batch is None:
-        qf, q_pids, q_camids = extract_features(model, query_batches, pool, local_only=True)
-        gf, g_pids, g_camids = extract_features(model, gallery_batches, pool, local_only=True)
+        qf, q_pids, q_camids = extract_features(model, query_batches, pool, local_only=True, frame_size=frame_size)
+        gf, g_pids, g_camids = extract_features(model, gallery_batches, pool, local_only=True, frame_size=frame_size)
     else:
-        qf, q_pids, q_camids = extract_features_packed(model, query_batches, clip_batch, pool, local_only=True)
-        gf, g_pids, g_camids = extract_features_packed(model, gallery_batches, clip_batch, pool, local_only=True)
+        qf, q_pids, q_camids = extract_features_packed(model, query_batches, clip_batch, pool, local_only=True, frame_size=frame_size)
+        gf, g_pids, g_camids = extract_features_packed(model, gallery_batches, clip_batch, pool, local_only=True, frame_size=frame_size)
     cmc, mAP = match_and_rank(qf, q_pids, q_camids, gf, g_pids, g_camids, dist_metric, max_rank,
                               getattr(model, "hip_precision", "fp32"), re_rank=re_rank, local_only=True)
     if verbose:

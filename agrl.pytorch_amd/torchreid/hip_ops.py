@@ -418,6 +418,310 @@ def resample_taps_device(in_size, out_size, device):
     return k, bounds
 
 
+# ---- baseline JPEG decode (include/agrl_hip.h, "JPEG": agrl_jpeg_decode_u8; the host side is torchreid/device_decode.py) -----
+JPEG_MAX_DIM = 4096       # the largest frame height / width the decoder takes
+JPEG_DESC = 16            # ints per descriptor row, columns below
+(JD_OFF, JD_LEN, JD_H, JD_W, JD_SAMP, JD_RI, JD_Q0, JD_DC0, JD_AC0, JD_WS) = (0, 1, 2, 3, 4, 5, 6, 9, 12, 15)
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3          # sampling codes
+JPEG_SCAN_ALIGN = 16      # every scan starts on a multiple of this in the byte buffer
+JPEG_SCAN_PAD = 16        # and at least this many zero bytes follow its last byte: the device reads whole 8-byte words
+JPEG_LOOK = 9             # bits of the Huffman look-ahead table
+JPEG_HUFF_WORDS = 360     # int32 words of one decode-ready Huffman table:
+JH_LOOK, JH_MAXCODE, JH_VALOFF, JH_VAL = 0, 256, 273, 290     # look[512] u16 (length << 8 | symbol, 0: longer than 9 bits) |
+#                                                                maxcode[17] | valoffset[17] | huffval[256] u8 (64 words); 6 spare
+JPEG_OK, JPEG_ERR_END, JPEG_ERR_CODE, JPEG_ERR_INDEX, JPEG_ERR_MARKER, JPEG_ERR_DESC = 0, 1, 2, 3, 4, 5
+JPEG_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                        35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
+                        62, 63], dtype=np.int64)   # natural index of the k-th coefficient of the stream
+
+
+def jpeg_frame_geometry(H, W, samp):
+    """The block geometry of one frame -> (ncomp, (h0, v0), [(blocks per row, block rows, cropped height, cropped width)] per component).
+    An interleaved scan covers whole MCUs of 8 h0 x 8 v0 pixels; a one-component scan has one block per MCU."""
+    h0, v0 = {JPEG_GRAY: (1, 1), JPEG_444: (1, 1), JPEG_422: (2, 1), JPEG_420: (2, 2)}[int(samp)]
+    mx, my = -(-W // (8 * h0)), -(-H // (8 * v0))
+    comps = [(mx * h0, my * v0, H, W)]
+    if samp != JPEG_GRAY:
+        comps += [(mx, my, -(-H // v0), -(-W // h0))] * 2
+    return len(comps), (h0, v0), comps
+
+
+def jpeg_frame_blocks(H, W, samp):
+    return sum(bw * bh for bw, bh, _, _ in jpeg_frame_geometry(H, W, samp)[2])
+
+
+class _JpegBits:
+    """The bit reader of the entropy decoder, as the kernel has it: a 64-bit window refilled bytewise, ``FF 00`` -> ``FF``; at any
+    other marker and at the end of the scan it stops consuming and feeds zero bits, and counts them (``fed``): a symbol that used one of
+    those has passed the end."""
+
+    def __init__(self, data):
+        self.d, self.n, self.p = data, len(data), 0
+        self.acc = self.nb = self.fed = 0
+        self.marker = False
+
+    def fill(self):
+        while self.nb <= 56:
+            b = 0
+            if not self.marker and self.p < self.n:
+                b = self.d[self.p]
+                if b == 0xFF:
+                    nxt = self.d[self.p + 1] if self.p + 1 < self.n else 0xFF   # a lone FF at the very end counts as a marker
+                    if nxt == 0:
+                        self.p += 2
+                    else:
+                        self.marker, b = True, 0
+                        self.fed += 8
+                else:
+                    self.p += 1
+            else:
+                self.fed += 8
+            self.acc = ((self.acc << 8) | b) & 0xFFFFFFFFFFFFFFFF
+            self.nb += 8
+
+    def peek(self, n):
+        return (self.acc >> (self.nb - n)) & ((1 << n) - 1)
+
+    def skip(self, n):
+        self.nb -= n
+
+    def passed_end(self):
+        return self.nb < self.fed
+
+    def restart(self, index):
+        """byte-align, consume FF D0+index -> True; False when whole bytes still stand in front of the marker or it is not there"""
+        real = self.nb - self.fed
+        if real >= 8 or self.p + 1 >= self.n or self.d[self.p] != 0xFF or self.d[self.p + 1] != 0xD0 + (index & 7):
+            return False
+        self.p += 2
+        self.acc = self.nb = self.fed = 0
+        self.marker = False
+        return True
+
+
+def jpeg_huffman_symbol(table, window):
+    """One symbol out of a decode-ready table row (int32 (JPEG_HUFF_WORDS,)): ``window`` holds the next 16 bits of the stream, MSB
+    first -> (code length, symbol), or (0, 0) when the bits are no code of the table. The 9-bit look-ahead first, then libjpeg's
+    maxcode / valoffset walk for the longer codes."""
+    look = table[JH_LOOK:JH_LOOK + 256].view(np.uint16)
+    e = int(look[window >> (16 - JPEG_LOOK)])
+    if e:
+        return e >> 8, e & 255
+    for l in range(JPEG_LOOK + 1, 17):
+        code = window >> (16 - l)
+        if code <= int(table[JH_MAXCODE + l]):
+            return l, int(table[JH_VAL:JH_VAL + 64].view(np.uint8)[(code + int(table[JH_VALOFF + l])) & 255])
+    return 0, 0
+
+
+def _jpeg_extend(v, s):
+    return v - (1 << s) + 1 if s and v < (1 << (s - 1)) else v
+
+
+def _jpeg_entropy_reference(scan, H, W, samp, ri, quant, dc, ac):
+    """One scan -> (coefficients int16 (blocks, 64) natural order, dequantised, component after component in raster block order; status).
+    ``quant`` / ``dc`` / ``ac``: the component's tables."""
+    ncomp, (h0, v0), comps = jpeg_frame_geometry(H, W, samp)
+    base = np.cumsum([0] + [bw * bh for bw, bh, _, _ in comps])
+    coef = np.zeros((int(base[-1]), 64), dtype=np.int16)
+    mx, my = -(-W // (8 * h0)), -(-H // (8 * v0))
+    br = _JpegBits(scan)
+    pred = [0] * ncomp
+    zz = JPEG_ZIGZAG.tolist()
+    q = [t.astype(np.int64).tolist() for t in quant]
+    for m in range(mx * my):
+        if ri and m and m % ri == 0:
+            if not br.restart(m // ri - 1):
+                return coef, JPEG_ERR_MARKER
+            pred = [0] * ncomp
+        for c in range(ncomp):
+            bw = comps[c][0]
+            hc, vc = (h0, v0) if c == 0 else (1, 1)
+            for blk in range(hc * vc):
+                row = coef[int(base[c]) + ((m // mx) * vc + blk // hc) * bw + (m % mx) * hc + blk % hc]
+                k = 0
+                while k < 64:
+                    br.fill()
+                    l, sym = jpeg_huffman_symbol(dc[c] if k == 0 else ac[c], br.peek(16))
+                    if l == 0:
+                        return coef, JPEG_ERR_CODE
+                    br.skip(l)
+                    r, s = (0, sym & 15) if k == 0 else (sym >> 4, sym & 15)
+                    if k and s == 0:
+                        if br.passed_end():
+                            return coef, JPEG_ERR_MARKER if br.marker else JPEG_ERR_END
+                        if r != 15:
+                            break          # EOB
+                        k += 16            # ZRL
+                        if k > 64:
+                            return coef, JPEG_ERR_INDEX
+                        continue
+                    k += r
+                    if k > 63:
+                        return coef, JPEG_ERR_INDEX
+                    v = _jpeg_extend(br.peek(s), s) if s else 0
+                    br.skip(s)
+                    if br.passed_end():
+                        return coef, JPEG_ERR_MARKER if br.marker else JPEG_ERR_END
+                    if k == 0:
+                        v = pred[c] = pred[c] + v
+                    w = (v * q[c][zz[k]]) & 0xFFFF          # stored as int16: the low 16 bits
+                    row[zz[k]] = w - 0x10000 if w >= 0x8000 else w
+                    k += 1
+    return coef, JPEG_OK
+
+
+def _jpeg_idct_pass(x, shift):
+    """libjpeg's accurate integer IDCT (jidctint.c, CONST_BITS 13) along axis 0 of an int32 (8, ...) array, descaled by ``shift``."""
+    z2, z3 = x[2], x[6]
+    z1 = (z2 + z3) * 4433
+    tmp2, tmp3 = z1 - z3 * 15137, z1 + z2 * 6270
+    tmp0, tmp1 = (x[0] + x[4]) << 13, (x[0] - x[4]) << 13
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    tmp0, tmp1, tmp2, tmp3 = x[7], x[5], x[3], x[1]
+    z1, z2, z3, z4 = tmp0 + tmp3, tmp1 + tmp2, tmp0 + tmp2, tmp1 + tmp3
+    z5 = (z3 + z4) * 9633
+    tmp0, tmp1, tmp2, tmp3 = tmp0 * 2446, tmp1 * 16819, tmp2 * 25172, tmp3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    tmp0, tmp1, tmp2, tmp3 = tmp0 + z1 + z3, tmp1 + z2 + z4, tmp2 + z2 + z3, tmp3 + z1 + z4
+    half = np.int32(1 << (shift - 1))
+    return np.stack([tmp10 + tmp3, tmp11 + tmp2, tmp12 + tmp1, tmp13 + tmp0, tmp13 - tmp0, tmp12 - tmp1, tmp11 - tmp2, tmp10 - tmp3]
+                    ) + half >> shift
+
+
+def _jpeg_idct_reference(coef):
+    """int16 (n, 64) dequantised blocks -> uint8 (n, 8, 8): columns (>> 11), rows (>> 18), + 128, clamped. int32 throughout."""
+    x = coef.astype(np.int32).reshape(-1, 8, 8)
+    with np.errstate(over="ignore"):
+        ws = _jpeg_idct_pass(x.transpose(1, 0, 2), 11)            # (row, n, col): along the columns
+        out = _jpeg_idct_pass(ws.transpose(2, 1, 0), 18)          # (col, n, row): along the rows
+    return np.clip(out.transpose(1, 2, 0) + 128, 0, 255).astype(np.uint8)
+
+
+def _jpeg_plane(samples, bw, bh, ph, pw):
+    """(bw bh, 8, 8) blocks in raster order -> the component plane, cropped to ph x pw"""
+    return samples.reshape(bh, bw, 8, 8).transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8)[:ph, :pw]
+
+
+def _jpeg_upsample_h(p, rnd_even, rnd_odd, shift, weight):
+    """the triangle filter along the last axis, edges replicated: out[2i] = (w p[i] + p[i-1] + rnd_even) >> shift, out[2i+1] likewise"""
+    last, nxt = np.concatenate([p[:, :1], p[:, :-1]], 1), np.concatenate([p[:, 1:], p[:, -1:]], 1)
+    out = np.empty((p.shape[0], 2 * p.shape[1]), dtype=np.int32)
+    out[:, 0::2] = (weight * p + last + rnd_even) >> shift
+    out[:, 1::2] = (weight * p + nxt + rnd_odd) >> shift
+    return out
+
+
+def _jpeg_upsample_reference(p, samp, H, W):
+    """a cropped chroma plane -> H x W, libjpeg's fancy upsampling"""
+    p = p.astype(np.int32)
+    if samp == JPEG_422:
+        return _jpeg_upsample_h(p, 1, 2, 2, 3)[:H, :W]
+    if samp == JPEG_420:
+        up, down = np.concatenate([p[:1], p[:-1]], 0), np.concatenate([p[1:], p[-1:]], 0)
+        rows = np.empty((2 * p.shape[0], p.shape[1]), dtype=np.int32)
+        rows[0::2], rows[1::2] = 3 * p + up, 3 * p + down           # colsum of output rows 2r and 2r + 1
+        return _jpeg_upsample_h(rows, 8, 7, 4, 3)[:H, :W]
+    return p
+
+
+def jpeg_decode_reference(plan):
+    """The decoder's arithmetic on the CPU, the definition agrl_jpeg_decode_u8 is held to bit for bit: ``plan`` (device_decode.JpegPlan)
+    -> (clip uint8 (F,Hc,Wc,3), status int32 (F)) as CPU tensors. Huffman decode per ITU T.81 out of the plan's decode-ready tables
+    (``_jpeg_entropy_reference``), libjpeg's accurate integer IDCT, its fancy chroma upsampling on planes cropped to the image, its
+    16-bit fixed-point YCbCr -> RGB. Pixels outside a frame's valid extent are 0. A frame whose status is not 0 stopped decoding there:
+    its pixels are what the coefficients decoded so far give."""
+    desc = np.asarray(plan.desc)
+    F = desc.shape[0]
+    Hc, Wc = int(plan.container[0]), int(plan.container[1])
+    out = np.zeros((F, Hc, Wc, 3), dtype=np.uint8)
+    status = np.zeros(F, dtype=np.int32)
+    for f in range(F):
+        d = desc[f].tolist()
+        H, W, samp = d[JD_H], d[JD_W], d[JD_SAMP]
+        ncomp, _, comps = jpeg_frame_geometry(H, W, samp)
+        scan = bytes(plan.scans[d[JD_OFF]:d[JD_OFF] + d[JD_LEN]])
+        coef, status[f] = _jpeg_entropy_reference(scan, H, W, samp, d[JD_RI], [plan.quant[d[JD_Q0 + c]] for c in range(ncomp)],
+                                                  [plan.huff[d[JD_DC0 + c]] for c in range(ncomp)],
+                                                  [plan.huff[d[JD_AC0 + c]] for c in range(ncomp)])
+        samples = _jpeg_idct_reference(coef)
+        planes, at = [], 0
+        for bw, bh, ph, pw in comps:
+            planes.append(_jpeg_plane(samples[at:at + bw * bh], bw, bh, ph, pw))
+            at += bw * bh
+        y = planes[0].astype(np.int32)
+        if ncomp == 1:
+            out[f, :H, :W] = y[:, :, None].astype(np.uint8)
+            continue
+        cb = _jpeg_upsample_reference(planes[1], samp, H, W) - 128
+        cr = _jpeg_upsample_reference(planes[2], samp, H, W) - 128
+        rgb = np.stack([y + ((91881 * cr + 32768) >> 16), y + ((-22554 * cb + 32768 - 46802 * cr) >> 16), y + ((116130 * cb + 32768) >> 16)], -1)
+        out[f, :H, :W] = np.clip(rgb, 0, 255).astype(np.uint8)
+    return torch.from_numpy(out), torch.from_numpy(status)
+
+
+def jpeg_workspace_bytes(plan):
+    """bytes of device workspace agrl_jpeg_decode_u8 needs for ``plan`` (agrl_jpeg_decode_workspace)"""
+    return int(_hip.lib().agrl_jpeg_decode_workspace(int(plan.ws_blocks)))
+
+
+def jpeg_decode(plan, out=None, device=None, workspace=None, operands=None):
+    """The same on the GPU (agrl_jpeg_decode_u8): ``plan`` is the HOST batch plan of device_decode.jpeg_batch_plan; its byte buffer,
+    descriptors and tables are uploaded non-blocking from pinned memory on the current stream (``operands``: what ``jpeg_upload`` returned,
+    for a caller that uploaded ahead) -> (clip uint8 (F,Hc,Wc,3), status int32 (F)) on the device; ``out``: the clip is written in place
+    when given. The entry point validates every descriptor row against the buffers before anything is launched. Three launches
+    (entropy decode, IDCT, upsample + colour), no synchronisation: the caller reads ``status`` when it wants to."""
+    F = int(plan.desc.shape[0])
+    Hc, Wc = int(plan.container[0]), int(plan.container[1])
+    if operands is None:
+        if device is None:
+            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+        operands = jpeg_upload(plan, device)
+    scans_d, desc_d, quant_d, huff_d = operands
+    device = scans_d.device
+    if out is None:
+        out = torch.empty((F, Hc, Wc, 3), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, Hc, Wc, 3) or out.device != device or not out.is_contiguous():
+        raise ValueError("jpeg_decode: out must be contiguous uint8 %s on %s" % ((F, Hc, Wc, 3), device))
+    status = torch.empty((F,), dtype=torch.int32, device=device)
+    if F == 0:
+        return out, status
+    need = jpeg_workspace_bytes(plan)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != device or not workspace.is_contiguous():
+        raise ValueError("jpeg_decode: workspace must be contiguous uint8 of at least %d bytes on %s" % (need, device))
+    desc_h = np.ascontiguousarray(plan.desc, dtype=np.int32)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * scans_d.numel() + 2.0 * need + 1.0 * out.numel()}   # workspace written, read once
+    with _dev(out):
+        call("agrl_jpeg_decode_u8", ptr(scans_d), scans_d.numel(), desc_h.ctypes.data, ptr(desc_d), F, ptr(quant_d), quant_d.shape[0],
+             ptr(huff_d), huff_d.shape[0], ptr(workspace), workspace.numel(), ptr(out), Hc, Wc, ptr(status), JPEG_STAGE_ALL, _stream(out))
+    return out, status
+
+
+JPEG_STAGE_ENTROPY, JPEG_STAGE_IDCT, JPEG_STAGE_COLOUR, JPEG_STAGE_ALL = 1, 2, 4, 7   # the stage mask of agrl_jpeg_decode_u8
+
+
+def jpeg_upload(plan, device):
+    """the plan's device operands -> (scans uint8, desc int32 (F,16), quant int16 (NQ,64), huff int32 (NH,360)) on ``device``: one pinned
+    staging buffer, one non-blocking copy on the current stream"""
+    parts = [np.ascontiguousarray(plan.scans, dtype=np.uint8), np.ascontiguousarray(plan.desc, dtype=np.int32).view(np.uint8).reshape(-1),
+             np.ascontiguousarray(plan.quant, dtype=np.uint16).view(np.uint8).reshape(-1),
+             np.ascontiguousarray(plan.huff, dtype=np.int32).view(np.uint8).reshape(-1)]
+    assert parts[0].size % JPEG_SCAN_ALIGN == 0
+    sizes = [p.size for p in parts]
+    host = torch.empty((sum(sizes),), dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else torch.empty((sum(sizes),), dtype=torch.uint8)
+    at = 0
+    for p in parts:
+        host[at:at + p.size] = torch.from_numpy(p)
+        at += p.size
+    dev = host.to(device, non_blocking=True)
+    a, b, c = sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2]
+    return (dev[:a], dev[a:b].view(torch.int32).view(-1, JPEG_DESC), dev[b:c].view(torch.int16).view(-1, 64),
+            dev[c:].view(torch.int32).view(-1, JPEG_HUFF_WORDS))
+
+
 def _stem_frames(x, mean, std):
     """The frames argument of the three stems: fp32 NCHW, or uint8 in either layout (normalised inside the kernel's input staging) ->
     (x, N, H, W, bytes per input element, (table, layout) or None)."""

@@ -148,6 +148,31 @@ int agrl_clip_resample_u8(const unsigned char* x, const int* geometry, unsigned 
  * fp64 arithmetic on its own. */
 int agrl_resample_taps_u8(int in, int out, int* k_out, int* bounds_out, agrl_stream_t stream);
 
+/* ---- JPEG: baseline decode of a batch of frames, bit-exact with libjpeg-turbo's default decode (Pillow's Image.open().convert('RGB')) ----
+ * The host parses headers only (torchreid/device_decode.py) and hands over
+ *   scans      : device bytes, the entropy-coded segments end to end; 8-byte aligned, every scan at a multiple of 8 with at least 8
+ *                readable bytes behind its last word (the kernel reads whole aligned 8-byte words)
+ *   desc       : device int32 (F, 16) rows -- scan offset, scan length, H, W, sampling code (0 grayscale, 1 4:4:4, 2 4:2:2 = luma 2x1,
+ *                3 4:2:0 = luma 2x2), restart interval, quant table index x 3, DC Huffman table index x 3, AC index x 3 (per component;
+ *                grayscale uses the first of each), first 8x8 block of the frame's workspace slice -- and desc_host, the same rows in HOST
+ *                memory: every row is validated there (offsets inside the buffer, sizes inside the container and 1..4096, table indices
+ *                inside the tables, workspace slices inside the workspace and not overlapping) before anything is launched
+ *   quant      : device uint16 (NQ, 64), natural (row-major) order
+ *   huff       : device int32 (NH, 360), libjpeg's decode-ready shape: 512 uint16 of a 9-bit look-ahead table (code length << 8 | symbol,
+ *                0 where the code is longer), maxcode[17] (-1: no code of that length), valoffset[17], 256 uint8 symbols
+ *   workspace  : device, 16-byte aligned, agrl_jpeg_decode_workspace(blocks of all frames) bytes: int16 dequantised coefficients
+ *                [frame][component][block][64], then the uint8 samples the IDCT makes of them
+ *   out        : device uint8 (F, Hc, Wc, 3); frame f's H x W pixels in the top-left corner of its slot, the rest of the slot zeroed
+ *   status     : device int32 (F): 0 decoded; 1 the bit reader passed the end of the scan; 2 a code in no table; 3 an AC index beyond 63;
+ *                4 a restart marker missing or another marker inside the scan; 5 the device copy of the descriptor failed the checks.
+ *                Decoding of that frame stopped there; nothing outside its workspace slice and its slot was written
+ *   stages     : bit mask of what to launch, 1 entropy decode | 2 IDCT | 4 upsampling + colour (7: all; the parts are for measurements)
+ * No address is formed from stream contents without a range check: the kernels are memory-safe for any scan bytes. */
+size_t agrl_jpeg_decode_workspace(int ws_blocks);
+int agrl_jpeg_decode_u8(const unsigned char* scans, long long scan_bytes, const int* desc_host, const int* desc, int F,
+                        const unsigned short* quant, int NQ, const int* huff, int NH, void* workspace, size_t workspace_bytes,
+                        unsigned char* out, int Hc, int Wc, int* status, int stages, agrl_stream_t stream);
+
 /* Implicit-GEMM convolution (1x1 or 3x3, stride 1|2) + folded BN + optional residual + optional
  * ReLU, NHWC in / NHWC out. One call == one (conv, bn[, +residual][, relu]) group of
  * Bottleneck.forward, torchreid/models/vmgn.py:45-65 (and the downsample branch :58-59).
