@@ -71,6 +71,7 @@ SIGNATURES = {
     "agrl_resample_taps_u8": [_i, _i, _p, _p, _p],
     "agrl_jpeg_decode_workspace": [_i],   # returns size_t
     "agrl_jpeg_decode_u8": [_p, C.c_longlong, _p, _p, _i, _p, _i, _p, _i, _p, C.c_size_t, _p, _i, _i, _p, _i, _p],
+    "agrl_png_decode_u8": [_p, C.c_longlong, _p, _p, _i, _p, _i, _i, _p, _i, _p],
     "agrl_split16_planes": [_p, _p, C.c_longlong, _i, _i, _p],
     "agrl_split16_weight_planes": [_p, _p, C.c_longlong, _i, _f, _p],
     "agrl_split16_weights_inloop": [_p, _p, C.c_longlong, _i, _p],

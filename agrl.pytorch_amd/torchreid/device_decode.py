@@ -20,12 +20,15 @@ already takes: uint8 channel-last frames in a padded container plus each frame's
 Rejected files and frames the device reports a non-zero status for (a broken scan) take the FALLBACK: Pillow on the host, when it can
 be imported; otherwise the error is raised with the frame's index. ``DeviceJpegDecoder`` logs how many frames took it.
 
-OUT OF SCOPE: PNG (iLIDS-VID, PRID2011), file reading, dataset classes.
+PNG (iLIDS-VID, PRID2011) has its own half of this module, below: ``parse_png``, ``png_batch_plan``, ``DevicePngDecoder``; and
+``DeviceImageDecoder`` takes a batch of both. OUT OF SCOPE: file reading, dataset classes.
 """
 from __future__ import annotations
 
 import io
 import logging
+import struct
+import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -377,3 +380,237 @@ class DeviceJpegDecoder:
             raise UnsupportedJpeg("frame %d: %s (and Pillow, the fallback, cannot be imported)" % (i, why))
         except OSError as e:     # what the reference's own read would raise for this file
             raise UnsupportedJpeg("frame %d: %s, and Pillow cannot decode it either: %s" % (i, why, e)) from e
+
+
+# ---- PNG (iLIDS-VID, PRID2011): the sibling of the JPEG decoder ------------------------------------------------------------------------
+# The host walks the CHUNKS of each file and never inflates; the device (hip_ops.png_decode, agrl_png_decode_u8) inflates the zlib
+# stream and undoes the row filters, byte for byte what Pillow returns (PNG is lossless: there is no arithmetic to argue about).
+#
+#     accepted                                                   rejected (UnsupportedPng, before anything touches the GPU)
+#     --------------------------------------------------------   ----------------------------------------------------------------
+#     bit depth 8, colour type 0 (grey, replicated to RGB as      colour types 3 (palette), 4 and 6 (alpha); bit depths 1, 2, 4, 16
+#     convert('RGB') does) and colour type 2 (RGB)                Adam7 interlacing; a tRNS chunk (transparency); an acTL chunk (APNG)
+#     non-interlaced, any number of IDAT chunks                   a chunk whose CRC does not match, a chunk that ends early
+#     any mix of stored / fixed / dynamic deflate blocks, any     an inflated size H * (1 + W * channels) above PNG_MAX_INFLATED, a
+#     declared window                                             dimension of 0 or above PNG_MAX_DIM; anything that is not a PNG
+#
+# Rejected files and frames the device reports a non-zero status for (hip_ops.PNG_STATUS_NAMES: every one of inflate's own rejections,
+# a wrong Adler-32, a filter byte above 4) take the same FALLBACK as JPEG: Pillow on the host, counted and logged.
+PNG_MAX_DIM = ops.PNG_MAX_DIM
+PNG_MAX_INFLATED = ops.PNG_MAX_INFLATED
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+class UnsupportedPng(ValueError):
+    """The byte string is not a PNG of the subset the device decodes."""
+
+
+PngFrame = namedtuple("PngFrame", "height width channels stream idat_sizes")
+PngFrame.__doc__ = """One parsed file. channels: 1 (grey) or 3 (RGB); stream: the IDAT payloads joined, ONE zlib stream (bytes), not
+inflated; idat_sizes: the payload length of each IDAT chunk, in order."""
+
+PngPlan = namedtuple("PngPlan", "streams desc sizes container boundaries")
+PngPlan.__doc__ = """The device operands of one batch, host side. streams: uint8 (bytes,), every zlib stream at a multiple of
+PNG_STREAM_ALIGN with at least PNG_STREAM_PAD zero bytes behind it; desc: int32 (F, 8) rows (stream offset, stream length, H, W,
+channels, three spare zeros); sizes: int64 (F, 2) = (H, W); container: (Hmax, Wmax); boundaries: per frame the byte offsets inside its
+stream where one IDAT chunk ended and the next began (host only: the restatement's coverage counters read them)."""
+
+_PNG_COLOUR = {3: "colour type 3 (palette)", 4: "colour type 4 (grey + alpha)", 6: "colour type 6 (RGB + alpha)"}
+
+
+def parse_png(data):
+    """Walk the chunks of one file -> PngFrame; UnsupportedPng, each case by its own message, for everything outside the subset in the
+    table above. Signature, IHDR fields and EVERY chunk's CRC (zlib.crc32) are checked; the IDAT payloads are joined and returned as
+    they are: nothing is inflated here."""
+    data = bytes(data) if not isinstance(data, (bytes, bytearray)) else data
+    if len(data) < 8 or bytes(data[:8]) != PNG_SIGNATURE:
+        raise UnsupportedPng("not a PNG: no signature at the start")
+    at, header, idat, seen_end = 8, None, [], False
+    while at < len(data) and not seen_end:
+        if at + 12 > len(data):
+            raise UnsupportedPng("a chunk ends early: %d bytes at byte %d where a chunk needs 12" % (len(data) - at, at))
+        n, kind = struct.unpack(">I4s", data[at:at + 8])
+        if at + 12 + n > len(data):
+            raise UnsupportedPng("a chunk ends early: %r at byte %d says %d bytes, %d are left" % (kind, at, n, len(data) - at - 12))
+        body = data[at + 8:at + 8 + n]
+        (crc,) = struct.unpack(">I", data[at + 8 + n:at + 12 + n])
+        if zlib.crc32(data[at + 4:at + 8 + n]) & 0xFFFFFFFF != crc:
+            raise UnsupportedPng("chunk CRC mismatch: %r at byte %d" % (kind, at))
+        if header is None and kind != b"IHDR":
+            raise UnsupportedPng("not a PNG: the first chunk is %r, not IHDR" % kind)
+        if kind == b"IHDR":
+            if header is not None or n != 13:
+                raise UnsupportedPng("a second IHDR, or one of %d bytes" % n)
+            W, H, depth, colour, comp, filt, lace = struct.unpack(">IIBBBBB", body)
+            if colour in _PNG_COLOUR or colour not in (0, 2):
+                raise UnsupportedPng("%s is not decoded on the device" % _PNG_COLOUR.get(colour, "colour type %d" % colour))
+            if depth != 8:
+                raise UnsupportedPng("bit depth %d: 8-bit samples only" % depth)
+            if lace != 0:
+                raise UnsupportedPng("Adam7 interlacing (interlace method %d) is not decoded on the device" % lace)
+            if comp != 0 or filt != 0:
+                raise UnsupportedPng("compression method %d, filter method %d: 0 and 0 only" % (comp, filt))
+            if H < 1 or W < 1 or H > PNG_MAX_DIM or W > PNG_MAX_DIM:
+                raise UnsupportedPng("a dimension of %d x %d: 1..%d each" % (H, W, PNG_MAX_DIM))
+            channels = 3 if colour == 2 else 1
+            if ops.png_frame_inflated(H, W, channels) > PNG_MAX_INFLATED:
+                raise UnsupportedPng("a frame of %d x %d x %d inflates to %d bytes: over the size bound PNG_MAX_INFLATED = %d" % (
+                    H, W, channels, ops.png_frame_inflated(H, W, channels), PNG_MAX_INFLATED))
+            header = (H, W, channels)
+        elif kind == b"tRNS":
+            raise UnsupportedPng("a tRNS chunk (transparency) is not decoded on the device")
+        elif kind == b"acTL":
+            raise UnsupportedPng("an acTL chunk (animated PNG) is not decoded on the device")
+        elif kind == b"IDAT":
+            idat.append(bytes(body))
+        elif kind == b"IEND":
+            seen_end = True
+        at += 12 + n
+    if header is None:
+        raise UnsupportedPng("not a PNG: no IHDR chunk")
+    if not idat:
+        raise UnsupportedPng("a PNG without an IDAT chunk")
+    return PngFrame(header[0], header[1], header[2], b"".join(idat), tuple(len(b) for b in idat))
+
+
+def png_batch_plan(frames):
+    """PngFrames -> PngPlan, the operands of ONE decode launch: the zlib streams laid end to end (aligned and zero-padded: the device
+    reads whole words, one ahead) and one descriptor row per frame."""
+    frames = list(frames)
+    desc = np.zeros((len(frames), ops.PNG_DESC), dtype=np.int32)
+    chunks, at, boundaries = [], 0, []
+    for f, fr in enumerate(frames):
+        n = len(fr.stream)
+        room = -(-(n + ops.PNG_STREAM_PAD) // ops.PNG_STREAM_ALIGN) * ops.PNG_STREAM_ALIGN
+        chunk = np.zeros(room, dtype=np.uint8)
+        chunk[:n] = np.frombuffer(fr.stream, dtype=np.uint8)
+        chunks.append(chunk)
+        d = desc[f]
+        d[ops.PD_OFF], d[ops.PD_LEN], d[ops.PD_H], d[ops.PD_W], d[ops.PD_CH] = at, n, fr.height, fr.width, fr.channels
+        boundaries.append(tuple(np.cumsum(fr.idat_sizes)[:-1].tolist()))
+        at += room
+        if at >= 2 ** 31:
+            raise ValueError("png_batch_plan: the batch is too large for one launch at frame %d (%d stream bytes)" % (f, at))
+    sizes = np.array([(fr.height, fr.width) for fr in frames], dtype=np.int64).reshape(len(frames), 2)
+    return PngPlan(np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.uint8), desc, sizes,
+                   (int(sizes[:, 0].max()) if len(frames) else 0, int(sizes[:, 1].max()) if len(frames) else 0), tuple(boundaries))
+
+
+class DevicePngDecoder:
+    """``DevicePngDecoder(device).decode(list_of_bytes, shape=None)``: the arguments, the return value and the counters of
+    ``DeviceJpegDecoder.decode``, for PNG files: ``(imgs uint8 (*shape, Hmax, Wmax, 3) on the device, sizes int64 (*shape, 2))``. Chunks
+    are walked and the batch planned on the host, the compressed bytes uploaded from pinned memory, and the device status is read ONCE
+    per call. Files outside the subset and frames with a non-zero status are decoded by Pillow on the host and copied into their slots;
+    where Pillow cannot decode a frame either (or cannot be imported), UnsupportedPng is raised with the frame's index. On a CPU
+    device the restatement (``hip_ops.png_decode_reference``) decodes: the same bytes."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.frames = self.fallback_frames = 0
+
+    def decode(self, encoded, shape=None):
+        encoded = list(encoded)
+        F = len(encoded)
+        shape = (F,) if shape is None else tuple(int(v) for v in shape)
+        if int(np.prod(shape, dtype=np.int64)) != F:
+            raise ValueError("DevicePngDecoder.decode: %d frames do not fill shape %s" % (F, shape))
+        parsed, fallback = [], {}
+        for i, data in enumerate(encoded):
+            try:
+                parsed.append((i, parse_png(data)))
+            except UnsupportedPng as e:
+                fallback[i] = self._fallback(i, data, e)
+        plan = png_batch_plan([fr for _, fr in parsed])
+        sizes = np.zeros((F, 2), dtype=np.int64)
+        for i, fr in parsed:
+            sizes[i] = (fr.height, fr.width)
+        for i, px in fallback.items():
+            sizes[i] = px.shape[:2]
+        Hc, Wc = (int(sizes[:, 0].max()), int(sizes[:, 1].max())) if F else (0, 0)
+        plan = plan._replace(container=(Hc, Wc))
+        if parsed:
+            if self.device.type == "cuda":
+                with torch.cuda.device(self.device):
+                    clip, status = ops.png_decode(plan, device=self.device)
+                status = status.cpu().numpy()          # the one synchronisation of the call
+            else:
+                clip, status = ops.png_decode_reference(plan)
+                status = status.numpy()
+        else:
+            clip, status = torch.zeros((0, Hc, Wc, 3), dtype=torch.uint8, device=self.device), np.zeros(0, dtype=np.int32)
+        for k in np.flatnonzero(status).tolist():
+            i = parsed[k][0]
+            fallback[i] = self._fallback(i, encoded[i], "device status %d (%s)" % (int(status[k]), ops.PNG_STATUS_NAMES[int(status[k])]))
+            if fallback[i].shape[:2] != tuple(sizes[i]):
+                raise UnsupportedPng("frame %d: Pillow decodes %s where the header says %s" % (i, fallback[i].shape[:2], tuple(sizes[i])))
+        if len(parsed) == F:
+            out = clip
+        else:
+            out = torch.zeros((F, Hc, Wc, 3), dtype=torch.uint8, device=self.device)
+            if parsed:
+                out[torch.as_tensor([i for i, _ in parsed], device=self.device)] = clip
+        if fallback:
+            host = torch.zeros((len(fallback), Hc, Wc, 3), dtype=torch.uint8)
+            for k, (i, px) in enumerate(sorted(fallback.items())):
+                host[k, :px.shape[0], :px.shape[1]] = torch.from_numpy(np.array(px, dtype=np.uint8))
+            out[torch.as_tensor(sorted(fallback), device=self.device)] = host.to(self.device)
+            log.warning("DevicePngDecoder: %d of %d frames took the Pillow fallback", len(fallback), F)
+        self.frames += F
+        self.fallback_frames += len(fallback)
+        return out.view(shape + (Hc, Wc, 3)), sizes.reshape(shape + (2,))
+
+    @staticmethod
+    def _fallback(i, data, why):
+        try:
+            return pillow_decode(data)
+        except ImportError:
+            if isinstance(why, UnsupportedPng):
+                raise UnsupportedPng("frame %d: %s (and Pillow, the fallback, cannot be imported)" % (i, why)) from why
+            raise UnsupportedPng("frame %d: %s (and Pillow, the fallback, cannot be imported)" % (i, why))
+        except (OSError, SyntaxError, ValueError) as e:     # what the reference's own read would raise for this file
+            raise UnsupportedPng("frame %d: %s, and Pillow cannot decode it either: %s" % (i, why, e)) from e
+
+
+class DeviceImageDecoder:
+    """``DeviceImageDecoder(device).decode(list_of_bytes, shape=None)``: a batch of JPEG and PNG files in any mix. Each frame's first
+    bytes decide: JPEG frames go to a ``DeviceJpegDecoder``, PNG frames (and whatever is neither: the PNG decoder's fallback names it)
+    to a ``DevicePngDecoder``; both results are merged into ONE container, with sizes, in the caller's order. ``frames`` and
+    ``fallback_frames`` are the sums of the two decoders' counters. It is what a caller passes as ``decode_batches(..., decoder=...)``."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.jpeg = DeviceJpegDecoder(device)
+        self.png = DevicePngDecoder(device)
+
+    @property
+    def frames(self):
+        return self.jpeg.frames + self.png.frames
+
+    @property
+    def fallback_frames(self):
+        return self.jpeg.fallback_frames + self.png.fallback_frames
+
+    def decode(self, encoded, shape=None):
+        encoded = list(encoded)
+        F = len(encoded)
+        shape = (F,) if shape is None else tuple(int(v) for v in shape)
+        if int(np.prod(shape, dtype=np.int64)) != F:
+            raise ValueError("DeviceImageDecoder.decode: %d frames do not fill shape %s" % (F, shape))
+        is_jpeg = [bytes(data[:2]) == b"\xff\xd8" for data in encoded]
+        parts = []
+        for dec, want in ((self.jpeg, True), (self.png, False)):
+            idx = [i for i in range(F) if is_jpeg[i] == want]
+            if idx:
+                imgs, sizes = dec.decode([encoded[i] for i in idx])
+                parts.append((idx, imgs, sizes))
+        Hc = max([p[1].shape[1] for p in parts], default=0)
+        Wc = max([p[1].shape[2] for p in parts], default=0)
+        sizes = np.zeros((F, 2), dtype=np.int64)
+        if len(parts) == 1 and parts[0][0] == list(range(F)):
+            out, sizes = parts[0][1], parts[0][2]
+        else:
+            out = torch.zeros((F, Hc, Wc, 3), dtype=torch.uint8, device=self.device)
+            for idx, imgs, sz in parts:
+                out[torch.as_tensor(idx, device=self.device), :imgs.shape[1], :imgs.shape[2]] = imgs
+                sizes[idx] = sz
+        return out.view(shape + (Hc, Wc, 3)), sizes.reshape(shape + (2,))

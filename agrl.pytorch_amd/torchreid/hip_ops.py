@@ -722,6 +722,363 @@ def jpeg_upload(plan, device):
             dev[c:].view(torch.int32).view(-1, JPEG_HUFF_WORDS))
 
 
+# ---- PNG decode (include/agrl_hip.h, "PNG": agrl_png_decode_u8; the host side is torchreid/device_decode.py) ------------------------
+PNG_MAX_DIM = 4096            # the largest frame height / width the decoder takes
+PNG_MAX_INFLATED = 131072     # the largest H * (1 + W * channels): the inflated stream of a frame lives in one workgroup's LDS
+PNG_DESC = 8                  # ints per descriptor row, columns below (three spare, zero)
+PD_OFF, PD_LEN, PD_H, PD_W, PD_CH = 0, 1, 2, 3, 4
+PNG_STREAM_ALIGN = 16         # every zlib stream starts on a multiple of this in the byte buffer
+PNG_STREAM_PAD = 16           # and at least this many zero bytes follow its last byte: the device reads whole 8-byte words, one ahead
+# the status codes: what png_decode_reference returns for each of inflate's own rejections (zlib's inflate.c / inftrees.c)
+(PNG_OK, PNG_ERR_INPUT, PNG_ERR_HEADER, PNG_ERR_BTYPE, PNG_ERR_STORED, PNG_ERR_DESC, PNG_ERR_COUNTS, PNG_ERR_OVERSUB, PNG_ERR_INCOMPLETE,
+ PNG_ERR_REPEAT, PNG_ERR_NOEOB, PNG_ERR_LITLEN, PNG_ERR_DISTSYM, PNG_ERR_DIST, PNG_ERR_SHORT, PNG_ERR_LONG, PNG_ERR_ADLER,
+ PNG_ERR_FILTER) = range(18)
+PNG_STATUS_NAMES = ("decoded", "input exhausted", "bad CMF / FLG", "block type 3", "stored LEN / NLEN mismatch", "descriptor row refused",
+                    "more than 286 literal/length or 30 distance symbols", "over-subscribed code set", "incomplete code set",
+                    "length repeat with nothing before it, or overrunning", "no end-of-block code", "invalid literal/length code",
+                    "invalid distance code", "distance before the start of the output", "output shorter than the frame",
+                    "output longer than the frame", "Adler-32 mismatch", "filter byte above 4")
+PNG_STAGE_INFLATE, PNG_STAGE_FILTER, PNG_STAGE_STORE, PNG_STAGE_ALL = 1, 2, 4, 7   # the stage mask of agrl_png_decode_u8
+_PNG_LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_PNG_LEXT = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+_PNG_DBASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289,
+              16385, 24577)
+_PNG_DEXT = (0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13)
+_PNG_CLORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_PNG_CODES, _PNG_LENS, _PNG_DISTS = 0, 1, 2
+_PNG_FIXED_LENS = np.array([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, dtype=np.int64)
+
+
+def png_frame_inflated(H, W, channels):
+    """bytes the zlib stream of an 8-bit non-interlaced frame inflates to: a filter byte and W * channels samples per row"""
+    return int(H) * (1 + int(W) * int(channels))
+
+
+def _png_code_table(lens, kind):
+    """Code lengths -> (status, table int32 (1 << maxbits,), maxbits): the canonical Huffman code of RFC 1951 3.2.2 as a flat look-up by
+    the next ``maxbits`` bits of the stream (LSB first); an entry is ``length << 16 | symbol``, 0 where no code starts with those bits.
+    inflate's own rejections (inftrees.c): an over-subscribed set; an incomplete one, except a distance set of ONE code of length 1;
+    a set with no code at all is accepted for distances (every look-up is an invalid code) and incomplete otherwise."""
+    lens = np.asarray(lens, dtype=np.int64)
+    count = np.bincount(lens, minlength=16)
+    maxbits = int(np.flatnonzero(count[1:]).max()) + 1 if count[1:].any() else 0
+    if maxbits == 0:
+        return (PNG_OK if kind == _PNG_DISTS else PNG_ERR_INCOMPLETE), np.zeros(2, dtype=np.int32), 1
+    left = 1
+    for l in range(1, 16):
+        left = (left << 1) - int(count[l])
+        if left < 0:
+            return PNG_ERR_OVERSUB, None, 0
+    if left > 0 and (kind != _PNG_DISTS or maxbits != 1):
+        return PNG_ERR_INCOMPLETE, None, 0
+    table = np.zeros(1 << maxbits, dtype=np.int32)
+    code = 0
+    nxt = [0] * 17
+    for l in range(1, 16):
+        code = (code + int(count[l - 1] if l > 1 else 0)) << 1
+        nxt[l] = code
+    for sym, l in enumerate(lens.tolist()):
+        if l:
+            c = nxt[l]
+            nxt[l] += 1
+            rev = int(format(c, "0%db" % l)[::-1], 2)
+            table[rev::1 << l] = (l << 16) | sym
+    return PNG_OK, table, maxbits
+
+
+class _PngBits:
+    """deflate's bit reader, LSB first; zeros beyond the end, and ``over`` once a field used one of them"""
+
+    def __init__(self, data):
+        self.n = len(data)
+        self.d = bytes(data) + b"\0" * 8
+        self.pos = 0
+
+    def peek(self, n):
+        p = self.pos >> 3
+        return (int.from_bytes(self.d[p:p + 4], "little") >> (self.pos & 7)) & ((1 << n) - 1) if p < self.n else 0
+
+    def take(self, n):
+        v = self.peek(n)
+        self.pos += n
+        return v
+
+    @property
+    def over(self):
+        return self.pos > 8 * self.n
+
+
+def _png_inflate_reference(stream, expected, counters=None, boundaries=()):
+    """One zlib stream (RFC 1950 / 1951) -> (the inflated bytes so far, status): exactly ``expected`` bytes for status 0. ``counters``: a
+    dict that receives what the stream exercised (block types, matches, ...); ``boundaries``: byte offsets inside the stream (where one
+    IDAT chunk ends and the next begins), for the counter of Huffman codes that straddle one."""
+    br = _PngBits(stream)
+    out = bytearray()
+    cnt = counters if counters is not None else {}
+    for k in ("blocks", "empty_stored", "max_len", "max_dist", "dist_lt_len", "dist_1", "split_codes"):
+        cnt.setdefault(k, 0)
+    cnt.setdefault("btypes", set())
+    edges = [8 * b for b in boundaries]
+
+    def code(table, bits):
+        at = br.pos
+        e = int(table[br.peek(bits)])
+        br.pos += (e >> 16) if e else 1
+        if e and any(at < b < br.pos for b in edges):
+            cnt["split_codes"] += 1
+        return e
+
+    cmf, flg = br.take(8), br.take(8)
+    if br.over:
+        return out, PNG_ERR_INPUT
+    if (cmf & 15) != 8 or (cmf >> 4) > 7 or ((cmf << 8) | flg) % 31 or (flg & 32):
+        return out, PNG_ERR_HEADER
+    cnt["wbits"] = (cmf >> 4) + 8
+    last = 0
+    while not last:
+        last, btype = br.take(1), br.take(2)
+        if br.over:
+            return out, PNG_ERR_INPUT
+        if btype == 3:
+            return out, PNG_ERR_BTYPE
+        cnt["blocks"] += 1
+        cnt["btypes"].add(btype)
+        if btype == 0:
+            br.pos = (br.pos + 7) & ~7
+            n, inv = br.take(16), br.take(16)
+            if br.over:
+                return out, PNG_ERR_INPUT
+            if n != (inv ^ 0xFFFF):
+                return out, PNG_ERR_STORED
+            at = br.pos >> 3
+            if at + n > br.n:
+                return out, PNG_ERR_INPUT
+            if len(out) + n > expected:
+                return out, PNG_ERR_LONG
+            out += br.d[at:at + n]
+            br.pos += 8 * n
+            cnt["empty_stored"] += n == 0
+            continue
+        if btype == 1:
+            lens, nlen, ndist = np.concatenate([_PNG_FIXED_LENS, np.full(32, 5, dtype=np.int64)]), 288, 32
+        else:
+            nlen, ndist, ncode = br.take(5) + 257, br.take(5) + 1, br.take(4) + 4
+            if br.over:
+                return out, PNG_ERR_INPUT
+            if nlen > 286 or ndist > 30:
+                return out, PNG_ERR_COUNTS
+            cl = np.zeros(19, dtype=np.int64)
+            for i in range(ncode):
+                cl[_PNG_CLORDER[i]] = br.take(3)
+            if br.over:
+                return out, PNG_ERR_INPUT
+            st, ctab, cbits = _png_code_table(cl, _PNG_CODES)
+            if st:
+                return out, st
+            lens = np.zeros(nlen + ndist, dtype=np.int64)
+            i = 0
+            while i < nlen + ndist:
+                e = code(ctab, cbits)
+                if br.over:
+                    return out, PNG_ERR_INPUT
+                sym = e & 0xFFFF
+                if sym < 16:
+                    lens[i] = sym
+                    i += 1
+                    continue
+                prev = 0
+                if sym == 16:
+                    if i == 0:
+                        return out, PNG_ERR_REPEAT
+                    prev, rep = int(lens[i - 1]), 3 + br.take(2)
+                elif sym == 17:
+                    rep = 3 + br.take(3)
+                else:
+                    rep = 11 + br.take(7)
+                if br.over:
+                    return out, PNG_ERR_INPUT
+                if i + rep > nlen + ndist:
+                    return out, PNG_ERR_REPEAT
+                lens[i:i + rep] = prev
+                i += rep
+            if lens[256] == 0:
+                return out, PNG_ERR_NOEOB
+        st, ltab, lbits = _png_code_table(lens[:nlen], _PNG_LENS)
+        if st:
+            return out, st
+        st, dtab, dbits = _png_code_table(lens[nlen:nlen + ndist], _PNG_DISTS)
+        if st:
+            return out, st
+        while True:
+            e = code(ltab, lbits)
+            if br.over:
+                return out, PNG_ERR_INPUT
+            sym = e & 0xFFFF
+            if e == 0 or sym > 285:
+                return out, PNG_ERR_LITLEN
+            if sym < 256:
+                if len(out) >= expected:
+                    return out, PNG_ERR_LONG
+                out.append(sym)
+                continue
+            if sym == 256:
+                break
+            n = _PNG_LBASE[sym - 257] + br.take(_PNG_LEXT[sym - 257])
+            if br.over:
+                return out, PNG_ERR_INPUT
+            e = code(dtab, dbits)
+            if br.over:
+                return out, PNG_ERR_INPUT
+            sym = e & 0xFFFF
+            if e == 0 or sym > 29:
+                return out, PNG_ERR_DISTSYM
+            dist = _PNG_DBASE[sym] + br.take(_PNG_DEXT[sym])
+            if br.over:
+                return out, PNG_ERR_INPUT
+            if dist > len(out):
+                return out, PNG_ERR_DIST
+            if len(out) + n > expected:
+                return out, PNG_ERR_LONG
+            start = len(out) - dist
+            out += bytes(out[start + k % dist] for k in range(n)) if dist < n else out[start:start + n]
+            cnt["max_len"], cnt["max_dist"] = max(cnt["max_len"], n), max(cnt["max_dist"], dist)
+            cnt["dist_lt_len"] += dist < n
+            cnt["dist_1"] += dist == 1
+    if len(out) < expected:
+        return out, PNG_ERR_SHORT
+    br.pos = (br.pos + 7) & ~7
+    hi, lo = br.take(16), br.take(16)
+    if br.over:
+        return out, PNG_ERR_INPUT
+    want = (((hi & 255) << 8 | hi >> 8) << 16) | (lo & 255) << 8 | lo >> 8
+    # Adler-32 as the device takes it: a = 1 + sum d_i, b = N + sum (N - i) d_i, any partition of the sums, modulo 65521
+    d = np.frombuffer(bytes(out), dtype=np.uint8).astype(np.uint64)
+    N = d.size
+    a = (1 + int(d.sum())) % 65521
+    b = (N + int((d * (N - np.arange(N, dtype=np.uint64))).sum() % 65521)) % 65521
+    if ((b << 16) | a) != want:
+        return out, PNG_ERR_ADLER
+    return out, PNG_OK
+
+
+def _png_unfilter_reference(raw, H, W, ch, counters=None):
+    """The inflated bytes of a frame -> (samples uint8 (H, W * ch), status): the PNG filters None, Sub, Up, Average, Paeth (PNG
+    specification, 9.2), bytes modulo 256, the row above the first being zeros"""
+    rb = W * ch
+    rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(H, 1 + rb)
+    out = np.zeros((H, rb), dtype=np.uint8)
+    prev = np.zeros(rb, dtype=np.int64)
+    for y in range(H):
+        ft = int(rows[y, 0])
+        if ft > 4:
+            return out, PNG_ERR_FILTER
+        if counters is not None:
+            counters.setdefault("filters", set()).add(ft)
+        x = rows[y, 1:].astype(np.int64)
+        if ft == 0:
+            cur = x
+        elif ft == 1:
+            cur = np.cumsum(x.reshape(W, ch), axis=0).reshape(rb) & 255
+        elif ft == 2:
+            cur = (x + prev) & 255
+        else:
+            cur = np.zeros(rb, dtype=np.int64)
+            xs, ps = x.tolist(), prev.tolist()
+            cs = [0] * rb
+            for i in range(rb):
+                a = cs[i - ch] if i >= ch else 0
+                b = ps[i]
+                if ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = ps[i - ch] if i >= ch else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cs[i] = (xs[i] + pred) & 255
+            cur[:] = cs
+        out[y] = cur
+        prev = cur
+    return out, PNG_OK
+
+
+def png_decode_reference(plan, info=None):
+    """The PNG decoder's arithmetic on the CPU and the definition of its status codes: ``plan`` (device_decode.PngPlan) -> (clip uint8
+    (F,Hc,Wc,3), status int32 (F)) as CPU tensors, the device's layout: a frame in the top-left corner of its slot, grey replicated to
+    RGB, zeros elsewhere. RFC 1950 / 1951 inflate with inflate's own rejections, then the five row filters, in plain Python / numpy;
+    zlib itself takes no part. A frame whose status is not 0 leaves its whole slot zero. ``info``: a list that receives one dict per
+    frame: ``inflated`` (the bytes, as far as they came) and what the stream exercised (``_png_inflate_reference``'s counters)."""
+    desc = np.asarray(plan.desc)
+    F = desc.shape[0]
+    Hc, Wc = int(plan.container[0]), int(plan.container[1])
+    out = np.zeros((F, Hc, Wc, 3), dtype=np.uint8)
+    status = np.zeros(F, dtype=np.int32)
+    for f in range(F):
+        d = desc[f].tolist()
+        H, W, ch = d[PD_H], d[PD_W], d[PD_CH]
+        counters = {}
+        if info is not None:
+            info.append(counters)
+        if (not (1 <= H <= min(PNG_MAX_DIM, Hc) and 1 <= W <= min(PNG_MAX_DIM, Wc) and ch in (1, 3)) or png_frame_inflated(H, W, ch) > PNG_MAX_INFLATED
+                or d[PD_OFF] < 0 or d[PD_LEN] < 0 or d[PD_OFF] % 8 or d[PD_OFF] + (d[PD_LEN] + 7) // 8 * 8 + 8 > plan.streams.size):
+            status[f] = PNG_ERR_DESC
+            continue
+        stream = bytes(plan.streams[d[PD_OFF]:d[PD_OFF] + d[PD_LEN]])
+        edges = plan.boundaries[f] if getattr(plan, "boundaries", None) is not None and f < len(plan.boundaries) else ()
+        raw, status[f] = _png_inflate_reference(stream, png_frame_inflated(H, W, ch), counters, edges)
+        counters["inflated"] = bytes(raw)
+        if status[f]:
+            continue
+        px, status[f] = _png_unfilter_reference(raw, H, W, ch, counters)
+        if status[f]:
+            continue
+        out[f, :H, :W] = px.reshape(H, W, ch) if ch == 3 else px.reshape(H, W, 1)
+    return torch.from_numpy(out), torch.from_numpy(status)
+
+
+def png_upload(plan, device):
+    """the plan's device operands -> (streams uint8, desc int32 (F,8)) on ``device``: one pinned staging buffer, one non-blocking copy
+    on the current stream"""
+    parts = [np.ascontiguousarray(plan.streams, dtype=np.uint8), np.ascontiguousarray(plan.desc, dtype=np.int32).view(np.uint8).reshape(-1)]
+    assert parts[0].size % PNG_STREAM_ALIGN == 0
+    n = parts[0].size + parts[1].size
+    host = torch.empty((n,), dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else torch.empty((n,), dtype=torch.uint8)
+    host[:parts[0].size] = torch.from_numpy(parts[0])
+    host[parts[0].size:] = torch.from_numpy(parts[1])
+    dev = host.to(device, non_blocking=True)
+    return dev[:parts[0].size], dev[parts[0].size:].view(torch.int32).view(-1, PNG_DESC)
+
+
+def png_decode(plan, out=None, device=None, operands=None, stages=PNG_STAGE_ALL):
+    """The same on the GPU (agrl_png_decode_u8): ``plan`` is the HOST batch plan of device_decode.png_batch_plan; its byte buffer and
+    descriptors are uploaded non-blocking from pinned memory on the current stream (``operands``: what ``png_upload`` returned, for a
+    caller that uploaded ahead) -> (clip uint8 (F,Hc,Wc,3), status int32 (F)) on the device; ``out``: the clip is written in place when
+    given. The entry point validates every descriptor row against the buffers before anything is launched. One launch, one wavefront
+    per frame, no workspace (the inflated stream lives in LDS), no synchronisation: the caller reads ``status`` when it wants to."""
+    F = int(plan.desc.shape[0])
+    Hc, Wc = int(plan.container[0]), int(plan.container[1])
+    if operands is None:
+        if device is None:
+            device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+        operands = png_upload(plan, device)
+    streams_d, desc_d = operands
+    device = streams_d.device
+    if out is None:
+        out = torch.empty((F, Hc, Wc, 3), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, Hc, Wc, 3) or out.device != device or not out.is_contiguous():
+        raise ValueError("png_decode: out must be contiguous uint8 %s on %s" % ((F, Hc, Wc, 3), device))
+    status = torch.empty((F,), dtype=torch.int32, device=device)
+    if F == 0:
+        return out, status
+    desc_h = np.ascontiguousarray(plan.desc, dtype=np.int32)
+    if _hip.PROFILE is not None:
+        _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * streams_d.numel() + 1.0 * out.numel()}
+    with _dev(out):
+        call("agrl_png_decode_u8", ptr(streams_d), streams_d.numel(), desc_h.ctypes.data, ptr(desc_d), F, ptr(out), Hc, Wc, ptr(status),
+             int(stages), _stream(out))
+    return out, status
+
+
 def _stem_frames(x, mean, std):
     """The frames argument of the three stems: fp32 NCHW, or uint8 in either layout (normalised inside the kernel's input staging) ->
     (x, N, H, W, bytes per input element, (table, layout) or None)."""

@@ -173,6 +173,26 @@ int agrl_jpeg_decode_u8(const unsigned char* scans, long long scan_bytes, const 
                         const unsigned short* quant, int NQ, const int* huff, int NH, void* workspace, size_t workspace_bytes,
                         unsigned char* out, int Hc, int Wc, int* status, int stages, agrl_stream_t stream);
 
+/* ---- PNG: decode of a batch of frames, bit-exact with Pillow's Image.open().convert('RGB') -------------------------------------------
+ * 8-bit grey or RGB, non-interlaced. The host walks the chunks only (torchreid/device_decode.py: signature, IHDR, every CRC) and hands over
+ *   streams    : device bytes, each frame's zlib stream (its IDAT payloads joined) end to end; 8-byte aligned, every stream at a multiple
+ *                of 8 with at least 8 readable bytes behind its last word (the kernel reads whole aligned 8-byte words, one ahead)
+ *   desc       : device int32 (F, 8) rows -- stream offset, stream length, H, W, channels (1 grey, 3 RGB), three spare -- and desc_host,
+ *                the same rows in HOST memory: every row is validated there (offsets inside the buffer, sizes inside the container and
+ *                1..4096, H * (1 + W * channels) <= 131072: the inflated stream lives in one workgroup's LDS) before the launch
+ *   out        : device uint8 (F, Hc, Wc, 3); frame f's H x W pixels in the top-left corner of its slot, grey replicated, the rest zeroed
+ *   status     : device int32 (F): 0 decoded; else the slot is all zero and the code names inflate's own rejection: 1 input exhausted;
+ *                2 bad CMF / FLG; 3 block type 3; 4 stored LEN / NLEN mismatch; 5 the device copy of the descriptor failed the checks;
+ *                6 more than 286 literal/length or 30 distance symbols; 7 over-subscribed code set; 8 incomplete code set; 9 a length
+ *                repeat with nothing before it or overrunning; 10 no end-of-block code; 11 invalid literal/length code; 12 invalid
+ *                distance code; 13 a distance before the start of the output; 14 / 15 output shorter / longer than H * (1 + W * channels);
+ *                16 Adler-32 mismatch; 17 a filter byte above 4
+ *   stages     : bit mask, 1 inflate (always) | 2 undo the row filters | 4 store into ``out`` (7: all; the parts are for measurements)
+ * One launch, one wavefront per frame, no workspace. No address is formed from stream contents without a range check: the kernel is
+ * memory-safe for any stream bytes. */
+int agrl_png_decode_u8(const unsigned char* streams, long long stream_bytes, const int* desc_host, const int* desc, int F,
+                       unsigned char* out, int Hc, int Wc, int* status, int stages, agrl_stream_t stream);
+
 /* Implicit-GEMM convolution (1x1 or 3x3, stride 1|2) + folded BN + optional residual + optional
  * ReLU, NHWC in / NHWC out. One call == one (conv, bn[, +residual][, relu]) group of
  * Bottleneck.forward, torchreid/models/vmgn.py:45-65 (and the downsample branch :58-59).
