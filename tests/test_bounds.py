@@ -4,7 +4,8 @@ max-normalised error bar lets through."""
 import pytest
 import torch
 
-from bounds import INT_SENTINEL, check_rounded, half_ulp, n_acc_for, poisoned_outputs
+import bounds
+from bounds import INT_SENTINEL, check_rounded, fenced, half_ulp, n_acc_for, poisoned_outputs
 
 LP_TYPES = [torch.float16, torch.bfloat16]
 
@@ -123,6 +124,189 @@ def test_poisoned_outputs_fills_and_restores():
     assert torch.empty is real
     with pytest.raises(AssertionError):   # an element nobody wrote fails any bound
         check_rounded(f, torch.zeros(3, 4, dtype=torch.float64), torch.ones(3, 4, dtype=torch.float64), 4, torch.float16)
+
+
+# ---- the fences of poisoned_outputs() and fenced(): every allocation between two canary bands -------------------------------------
+BAND = 4096   # the self-tests use the smallest band; the default is checked once
+
+
+def _patched():
+    return (torch.empty, torch.empty_like, torch.zeros, torch.zeros_like, torch.Tensor.new_zeros)
+
+
+def test_fenced_outputs_clean_use_passes_and_everything_is_restored():
+    real = _patched()
+    base = torch.arange(6.0)
+    with poisoned_outputs(band=BAND):
+        f = torch.empty((3, 5), dtype=torch.float16)
+        g = torch.empty(2, 3, dtype=torch.bfloat16)
+        d = torch.empty(7)                                   # the default dtype
+        i = torch.empty(5, dtype=torch.int64)
+        b = torch.empty((9,), dtype=torch.uint8)
+        like = torch.empty_like(base, dtype=torch.float32)
+        z = torch.zeros((4, 3), dtype=torch.float32)
+        zl = torch.zeros_like(base)
+        nz = base.new_zeros((2, 2))
+        nzi = base.new_zeros(3, dtype=torch.int32)
+        f[1, 2] = 1.0                                        # a store to the interior is the kernel's business
+        z += 2.0
+    assert _patched() == real
+    for t, shape, dtype in ((f, (3, 5), torch.float16), (g, (2, 3), torch.bfloat16), (d, (7,), torch.float32),
+                            (i, (5,), torch.int64), (b, (9,), torch.uint8), (like, (6,), torch.float32),
+                            (z, (4, 3), torch.float32), (zl, (6,), torch.float32), (nz, (2, 2), torch.float32),
+                            (nzi, (3,), torch.int32)):
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device.type == "cpu"
+        assert t.data_ptr() % 64 == 0                        # the alignment of a fresh CPU allocation
+        assert t.untyped_storage().nbytes() == 2 * BAND + t.numel() * t.element_size()   # carved, tail band not rounded up
+    assert float(f[1, 2]) == 1.0 and int(torch.isnan(f).sum()) == 14
+    assert torch.isnan(g).all() and torch.isnan(d).all() and torch.isnan(like).all()
+    assert (i == INT_SENTINEL).all() and (b == 0x5A).all()
+    assert (z == 2.0).all() and (zl == 0).all() and (nz == 0).all() and (nzi == 0).all()
+
+
+def test_fenced_outputs_default_band_is_one_256_row_tile_of_512_16_bit_channels():
+    assert bounds.DEFAULT_BAND == 256 * 512 * 2 and bounds.DEFAULT_BAND % 4096 == 0
+    with poisoned_outputs():
+        t = torch.empty(3, dtype=torch.float16)
+    assert t.storage_offset() * 2 == bounds.DEFAULT_BAND and t.untyped_storage().nbytes() == 2 * bounds.DEFAULT_BAND + 6
+    for bad in (0, 100, 4096 + 512, -4096):
+        with pytest.raises(AssertionError, match="multiple of 4096"):
+            with poisoned_outputs(band=bad):
+                pass
+
+
+def _beyond(t, first, count):
+    """The fake kernel's view: ``count`` elements of t's storage starting ``first`` elements from t's start."""
+    return torch.as_strided(t, (count,), (1,), t.storage_offset() + first)
+
+
+def test_fenced_outputs_reject_one_element_past_the_end():
+    with pytest.raises(AssertionError, match=r"allocation 1 \(shape \(3, 5\), torch.float16\): 2 byte\(s\) modified AFTER the "
+                                             r"tensor, first at 0 and last at 1 bytes relative to its end"):
+        with poisoned_outputs(band=BAND):
+            torch.empty(4)
+            t = torch.empty((3, 5), dtype=torch.float16)
+            _beyond(t, 15, 1).fill_(1.0)
+
+
+def test_fenced_outputs_reject_one_element_before_the_start():
+    with pytest.raises(AssertionError, match=r"allocation 0 \(shape \(6,\), torch.float32\): 4 byte\(s\) modified BEFORE the "
+                                             r"tensor, first at -4 and last at -1 bytes relative to its start"):
+        with poisoned_outputs(band=BAND):
+            t = torch.zeros(6)
+            _beyond(t, -1, 1).fill_(1.0)
+
+
+def test_fenced_outputs_reject_the_last_byte_of_the_tail_band():
+    with pytest.raises(AssertionError, match=r"allocation 0 \(shape \(10,\), torch.uint8\): 1 byte\(s\) modified AFTER the "
+                                             r"tensor, first at %d and last at %d bytes relative to its end" % (BAND - 1, BAND - 1)):
+        with poisoned_outputs(band=BAND):
+            t = torch.empty(10, dtype=torch.uint8)
+            _beyond(t, 10 + BAND - 1, 1).fill_(0)
+    # ... and a ragged overrun reports its whole extent: rows of 3 floats written 2 rows too far
+    with pytest.raises(AssertionError, match=r"24 byte\(s\) modified AFTER the tensor, first at 0 and last at 23 bytes"):
+        with poisoned_outputs(band=BAND):
+            t = torch.empty((5, 3))
+            _beyond(t, 0, 21).fill_(0.5)
+
+
+def test_fenced_outputs_accept_interior_writes_and_leave_the_body_s_own_failure_alone():
+    with poisoned_outputs(band=BAND):
+        t = torch.empty((5, 3))
+        _beyond(t, 0, 15).fill_(0.5)
+        t2 = torch.empty_like(t)
+        t2.copy_(t)
+    assert (t == 0.5).all() and (t2 == 0.5).all()
+    real = _patched()
+    with pytest.raises(ZeroDivisionError):   # the block's own exception is not replaced by a fence report
+        with poisoned_outputs(band=BAND):
+            t = torch.empty(3)
+            _beyond(t, 3, 1).fill_(1.0)
+            1 / 0
+    assert _patched() == real
+
+
+def test_fenced_outputs_handle_zero_sized_non_contiguous_and_channels_last():
+    base = torch.arange(24.0).reshape(4, 6)
+    with poisoned_outputs(band=BAND):
+        e = torch.empty((0, 7), dtype=torch.float16)
+        e2 = torch.empty(0)
+        z = torch.zeros((3, 0), dtype=torch.int32)
+        nc = torch.empty_like(base.t())                                       # keeps the permuted strides: passed through
+        sl = torch.empty_like(base[:, ::2])                                   # a strided slice densifies: fenced
+        cl = torch.empty((2, 3, 4, 5), memory_format=torch.channels_last)     # passed through
+        zc = torch.zeros_like(base.t())
+    assert tuple(e.shape) == (0, 7) and e.dtype == torch.float16 and tuple(e2.shape) == (0,) and tuple(z.shape) == (3, 0)
+    assert tuple(nc.shape) == (6, 4) and torch.isnan(nc).all()
+    assert tuple(sl.shape) == (4, 3) and sl.is_contiguous() and torch.isnan(sl).all()
+    assert sl.untyped_storage().nbytes() == 2 * BAND + 48
+    assert cl.is_contiguous(memory_format=torch.channels_last) and torch.isnan(cl).all()
+    assert tuple(zc.shape) == (6, 4) and (zc == 0).all()
+    with pytest.raises(AssertionError, match=r"allocation 0 \(shape \(0, 7\), torch.float16\).*AFTER the tensor, first at 0"):
+        with poisoned_outputs(band=BAND):        # a zero-sized output still has its bands: any store is outside it
+            e = torch.empty((0, 7), dtype=torch.float16)
+            _beyond(e, 0, 1).fill_(1.0)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32, torch.int32, torch.int64, torch.uint8])
+@pytest.mark.parametrize("fill", [0x00, 0xFF, 0x7C])
+def test_fenced_round_trips_the_bits_between_bands_of_the_fill(dtype, fill):
+    g = torch.Generator().manual_seed(5)
+    src = torch.randint(0, 256, (7 * 3 * dtype.itemsize,), generator=g, dtype=torch.uint8).view(dtype).reshape(7, 3)   # NaNs too
+    t = src.t()                                                              # a non-contiguous operand
+    out = fenced(t, fill, band=BAND)
+    assert out.shape == t.shape and out.dtype == dtype and out.is_contiguous() and out.device == t.device
+    assert torch.equal(out.view(torch.uint8), t.contiguous().view(torch.uint8))
+    raw = torch.empty(0, dtype=torch.uint8).set_(out.untyped_storage())
+    n = out.numel() * dtype.itemsize
+    assert raw.numel() == 2 * BAND + n and out.storage_offset() * dtype.itemsize == BAND
+    assert (raw[:BAND] == fill).all() and (raw[BAND + n:] == fill).all()
+    # what the fills mean to a kernel that reads past an operand
+    if fill == 0xFF and dtype.is_floating_point:
+        assert torch.isnan(raw[:dtype.itemsize].view(dtype)).all()
+    if fill == 0xFF and not dtype.is_floating_point and dtype != torch.uint8:
+        assert int(raw[:dtype.itemsize].view(dtype)) == -1
+    if fill == 0x7C and dtype == torch.float16:
+        assert torch.isnan(raw[:2].view(dtype)).all()
+    if fill == 0x7C and dtype in (torch.bfloat16, torch.float32):
+        assert 1e36 < float(raw[:dtype.itemsize].view(dtype)) < 1e37
+
+
+def test_fenced_keeps_zero_sized_operands_and_the_default_band():
+    out = fenced(torch.zeros((0, 4), dtype=torch.int32), 0xFF)
+    assert tuple(out.shape) == (0, 4) and out.untyped_storage().nbytes() == 2 * bounds.DEFAULT_BAND
+
+
+def test_every_launching_entry_point_has_a_fence_case():
+    """tests/test_gpu_fences.py declares, family by family, the entry points its host-path calls reach (and holds that against
+    the calls really made, on the GPU). Here the declaration is held against the signature table: every entry point that takes
+    a stream is reached by a family, except the read yardstick; nothing is declared that the table does not have."""
+    import test_gpu_fences as T
+    from torchreid import _hip
+    launching = T.launching_entry_points()
+    assert T.NOT_FENCED == {"agrl_diag_read_stream"} and T.NOT_FENCED <= launching
+    # what does not launch: size queries, plans, switches -- none of them takes a stream
+    quiet = set(_hip.SIGNATURES) - launching
+    assert quiet == {"agrl_jpeg_decode_workspace", "agrl_bottleneck_seam_packed_bytes", "agrl_bottleneck_chain_enabled", "agrl_conv3x3_packed_bytes",
+                     "agrl_conv1x1_packed_bytes", "agrl_col_sum_workspace", "agrl_re_ranking_workspace", "agrl_distmat_topk_workspace",
+                     "agrl_bn_workspace", "agrl_conv_wgrad_workspace", "agrl_conv_wgrad_plan", "agrl_optim_geometry"}, sorted(quiet)
+    declared = set(T.ENTRY_POINTS)
+    assert declared <= launching, "declared but not in the signature table: %s" % sorted(declared - launching)
+    missing = launching - declared - T.NOT_FENCED
+    assert not missing, "entry points without a fence case in tests/test_gpu_fences.py: %s" % sorted(missing)
+    for name, fams in T.ENTRY_POINTS.items():
+        assert fams and all(f in T.FAMILIES and name in T.FAMILIES[f].entry_points for f in fams), name
+    # every family enters checks 2 and 3; only the byte kernels and the optimisers, banded by their own tests, stay out of check 1
+    unfenced = {n for n, f in T.FAMILIES.items() if not f.fence_outputs}
+    assert {ep for n in unfenced for ep in T.FAMILIES[n].entry_points} == {
+        "agrl_frames_normalize_u8", "agrl_frames_normalize_erase_u8", "agrl_clip_resample_u8", "agrl_jpeg_decode_u8", "agrl_png_decode_u8",
+        "agrl_adam_step", "agrl_sgd_step", "agrl_rmsprop_step", "agrl_adabound_step", "agrl_radam_step"}
+    assert set(T.NAMES) == set(T.FAMILIES) and set(T.FENCED) == set(T.FAMILIES) - unfenced
+    # only the split-fp16 plane families may skip, and only on the bf16 build
+    assert {ep for f in T.FAMILIES.values() if f.fp16_only for ep in f.entry_points} <= {
+        "agrl_split16_planes", "agrl_split16_weight_planes", "agrl_conv1x1_pack", "agrl_conv3x3_pack", "agrl_conv1x1_split16", "agrl_conv1x1_split16_dual",
+        "agrl_conv1x1_split16_pool", "agrl_conv3x3_packed_split16", "agrl_distmat_split16", "agrl_conv1x1_dual_split16", "agrl_row_sqnorm",
+        "agrl_row_l2_normalize"}
 
 
 # ---- tests/train_ref.py: the float64 references of the train-step kernels -----------------------------------------------------
