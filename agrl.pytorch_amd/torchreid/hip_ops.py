@@ -65,6 +65,15 @@ def _dev(t):
     return torch.cuda.device(t.device)
 
 
+def written(tensors):
+    """The rule for every raw writer: a kernel writes through a pointer, which torch's version counters do not see, so a wrapper that
+    had a kernel write tensors it did NOT allocate itself -- parameters, optimiser state, running statistics, a caller's ``out=`` --
+    calls this on them after the launch. The writes then count as torch's own in-place operations do: whatever is keyed on
+    ``_version`` (the pack cache's fingerprint in models/_resnet_hip.py, QueryOperandCache below) misses, and autograd refuses a
+    backward whose saved tensors were written underneath it. Host only, one call for any number of tensors."""
+    torch.autograd.graph.increment_version(tensors)
+
+
 PIXEL_MEAN = (0.485, 0.456, 0.406)   # the reference's transform_test: Normalize(mean, std) behind ToTensor
 PIXEL_STD = (0.229, 0.224, 0.225)    # (train_vidreid_xent_htri.py:214-217)
 
@@ -395,6 +404,7 @@ def clip_resample(frames, geometry, out_hw, out=None):
         raise ValueError("clip_resample: output size %dx%d, 1..%d each" % (OH, OW, RESAMPLE_MAX_OUT))
     N, Hs, Ws = frames.shape[:3]
     geo = torch.from_numpy(resample_geometry(geometry, frames.shape, (OH, OW), RESAMPLE_MAX_SCALE))
+    handed = out is not None
     if out is None:
         out = torch.empty((N, OH, OW, 3), dtype=torch.uint8, device=frames.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (N, OH, OW, 3) or out.device != frames.device or not out.is_contiguous():
@@ -406,6 +416,8 @@ def clip_resample(frames, geometry, out_hw, out=None):
         _hip.PROFILE_TAG = {"flops": 0.0, "bytes": 1.0 * frames.numel() + 1.0 * out.numel()}
     with _dev(frames):
         call("agrl_clip_resample_u8", ptr(frames), ptr(geo_d), ptr(out), N, Hs, Ws, OH, OW, _stream(frames))
+    if handed:
+        written(out)
     return out
 
 
@@ -679,6 +691,7 @@ def jpeg_decode(plan, out=None, device=None, workspace=None, operands=None):
         operands = jpeg_upload(plan, device)
     scans_d, desc_d, quant_d, huff_d = operands
     device = scans_d.device
+    handed = out is not None
     if out is None:
         out = torch.empty((F, Hc, Wc, 3), dtype=torch.uint8, device=device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (F, Hc, Wc, 3) or out.device != device or not out.is_contiguous():
@@ -697,6 +710,8 @@ def jpeg_decode(plan, out=None, device=None, workspace=None, operands=None):
     with _dev(out):
         call("agrl_jpeg_decode_u8", ptr(scans_d), scans_d.numel(), desc_h.ctypes.data, ptr(desc_d), F, ptr(quant_d), quant_d.shape[0],
              ptr(huff_d), huff_d.shape[0], ptr(workspace), workspace.numel(), ptr(out), Hc, Wc, ptr(status), JPEG_STAGE_ALL, _stream(out))
+    if handed:
+        written(out)  # (the workspace is scratch: nothing reads it after the call)
     return out, status
 
 
@@ -1063,6 +1078,7 @@ def png_decode(plan, out=None, device=None, operands=None, stages=PNG_STAGE_ALL)
         operands = png_upload(plan, device)
     streams_d, desc_d = operands
     device = streams_d.device
+    handed = out is not None
     if out is None:
         out = torch.empty((F, Hc, Wc, 3), dtype=torch.uint8, device=device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (F, Hc, Wc, 3) or out.device != device or not out.is_contiguous():
@@ -1076,6 +1092,8 @@ def png_decode(plan, out=None, device=None, operands=None, stages=PNG_STAGE_ALL)
     with _dev(out):
         call("agrl_png_decode_u8", ptr(streams_d), streams_d.numel(), desc_h.ctypes.data, ptr(desc_d), F, ptr(out), Hc, Wc, ptr(status),
              int(stages), _stream(out))
+    if handed:
+        written(out)
     return out, status
 
 
@@ -1352,6 +1370,7 @@ def distmat_split16(q3, g3, metric, g_unscale, qn=None, gn=None, out=None):
     m, D3 = q3.shape
     n = g3.shape[0]
     assert g3.shape[1] == D3 and q3.dtype == torch.float16 and g3.dtype == torch.float16
+    handed = out is not None
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=q3.device)
     code = METRIC_EUCLIDEAN if metric == "euclidean" else METRIC_COSINE
@@ -1363,6 +1382,8 @@ def distmat_split16(q3, g3, metric, g_unscale, qn=None, gn=None, out=None):
     with _dev(q3):
         call("agrl_distmat_split16", ptr(q3), ptr(g3), ptr(qn), ptr(gn), out.data_ptr(), m, n, D3, out.stride(0), code, float(g_unscale),
              ptr(ws), 0 if ws is None else ws.numel() * 4, _stream(q3))
+    if handed:
+        written(out)
     return out
 
 
@@ -1564,6 +1585,7 @@ def bottleneck_chain(z, a, table, n, work=None, out=None):
     assert 1 <= n <= CHAIN_MAX and table.dtype == torch.int64 and tuple(table.shape[1:]) == (8,) and table.shape[0] >= n
     assert z.dtype == LP_DTYPE and a.dtype == LP_DTYPE and tuple(z.shape) == (F, 16, 8, 256) and tuple(a.shape) == (F, 16, 8, 1024)
     assert z.is_contiguous() and a.is_contiguous()
+    handed = ([] if out is None else [out]) + ([] if work is None else list(work[:n - 1]))     # the caller's buffers: bumped below
     if work is None:
         work = [torch.empty_like(a) for _ in range(n - 1)]
     assert len(work) >= n - 1 and all(w.dtype == a.dtype and w.numel() == a.numel() and w.is_contiguous() for w in work[:n - 1])
@@ -1577,6 +1599,8 @@ def bottleneck_chain(z, a, table, n, work=None, out=None):
                             "bytes": 2.0 * (z.numel() + zn.numel() + (2 * n) * a.numel()) + n * 2.0 * (9 * 256 * 256 + 2 * 256 * 1024)}
     with _dev(z):
         call("agrl_bottleneck_chain", ptr(z), ptr(a), ptr(table), bufs, ptr(zn), F, n, _stream(z))
+    if handed:
+        written(handed)
     return out, zn
 
 
@@ -2198,6 +2222,8 @@ def clip_pool_ragged(feats, offsets, mode="avg", nonfinite=None):
     off_d = torch.from_numpy(off).pin_memory().to(feats.device, non_blocking=True)
     with _dev(feats):
         call("agrl_clip_pool_ragged", ptr(feats), ptr(off_d), ptr(out), ptr(nonfinite), N, T, D, 0 if mode == "avg" else 1, _stream(feats))
+    if nonfinite is not None:
+        written(nonfinite)
     return out
 
 
@@ -2313,6 +2339,7 @@ def distmat(q, g, metric, qn=None, gn=None, out=None):
     m, D = q.shape
     n, D2 = g.shape
     assert D == D2 and q.dtype == g.dtype
+    handed = out is not None
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=q.device)
     assert out.stride(1) == 1 and out.dtype == torch.float32
@@ -2327,6 +2354,8 @@ def distmat(q, g, metric, qn=None, gn=None, out=None):
     with _dev(q):
         _hip.call("agrl_distmat", ptr(q), ptr(g), ptr(qn), ptr(gn), out.data_ptr(), m, n, D, out.stride(0), code,
                   dtype_code(q.dtype), ptr(ws), 0 if ws is None else ws.numel() * 4, _stream(q))
+    if handed:
+        written(out)
     return out
 
 
@@ -2521,6 +2550,9 @@ def bn_fold_train(mean, var, gamma, beta, eps, momentum, n, running_mean=None, r
     with _dev(mean):
         call("agrl_bn_fold_train", ptr(mean), ptr(var), ptr(gamma), ptr(beta), float(eps), float(momentum), int(n), ptr(running_mean),
              ptr(running_var), ptr(num_batches_tracked), ptr(scale), ptr(shift), ptr(invstd), Cc, _stream(mean))
+    running = [t for t in (running_mean, running_var, num_batches_tracked) if t is not None]
+    if running:
+        written(running)      # the module's buffers: the eval forward's pack is folded from them
     return scale, shift, invstd
 
 

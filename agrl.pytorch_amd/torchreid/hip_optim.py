@@ -216,6 +216,28 @@ class NativeStepMixin(object):
         _hip.lib()
         return loss, (getattr(self, "zero_grads", False) if zero_grads is None else bool(zero_grads))
 
+    @staticmethod
+    def _mark_written(ops, recs, zero):
+        """After the launches of a step: the kernels wrote the parameters, the state tensors and, with ``zero``, the gradients of ``recs``
+        through raw pointers. One version bump over all of them (hip_ops.written) makes the step visible the way torch.optim's is: the
+        eval forward's pack cache rebuilds (models/_resnet_hip.fingerprint), and a backward through a graph recorded before the step
+        raises torch's in-place-modification error instead of differentiating against the stepped weights."""
+        tensors = []
+        for rec in recs:
+            tensors.append(rec.p)
+            if rec.s0 is not None:
+                tensors.append(rec.s0)
+            if rec.s1 is not None:
+                tensors.append(rec.s1)
+            if rec.s2 is not None:
+                tensors.append(rec.s2)
+            if zero:
+                g = rec.g()
+                if g is not None:
+                    tensors.append(g)
+        if tensors:
+            ops.written(tensors)
+
 
 class _Record(object):
     """What a step learned about one parameter, trusted again while the very same tensor objects sit at the very same addresses:
@@ -295,6 +317,7 @@ class HipAdam(NativeStepMixin, torch.optim.Adam):
             tensors, chunks = self._tables_for(device, rows)
             ops.adam_step(tensors, chunks, float(group["weight_decay"]), *adam_constants(float(group["lr"]), beta1, beta2, t),
                           float(group["eps"]), group["amsgrad"], zero)
+        self._mark_written(ops, counted, zero)
         return loss
 
 
@@ -333,13 +356,14 @@ class HipSGD(NativeStepMixin, torch.optim.SGD):
                         continue
                 self._check_tensors(p, g)
                 items.append((gi, rec, (p, g, momentum)))
-        classes = collections.OrderedDict()
+        classes, stepped = collections.OrderedDict(), []
         for gi, rec, todo in items:
             first = False
             if todo is not None:
                 p, g, momentum = todo
                 rec = recs[id(p)] = rec if rec is not None else _Record()
                 rec.p, rec.g, rec.s0, rec.device, buf = p, weakref.ref(g), None, p.device, 0
+                rec.s1 = rec.s2 = None
                 if momentum:
                     state = self.state[p]
                     first = state.get("momentum_buffer") is None
@@ -348,6 +372,7 @@ class HipSGD(NativeStepMixin, torch.optim.SGD):
                     rec.s0 = state["momentum_buffer"]
                     buf = self._check_state(p, rec.s0, "momentum_buffer")
                 rec.row = (p.data_ptr(), g.data_ptr(), buf, 0, 0, p.numel())
+            stepped.append(rec)
             if rec.row[5] > 0:
                 classes.setdefault((gi, rec.device, first), []).append(rec.row)
         for (gi, device, first), rows in classes.items():
@@ -355,6 +380,7 @@ class HipSGD(NativeStepMixin, torch.optim.SGD):
             tensors, chunks = self._tables_for(device, rows)
             ops.sgd_step(tensors, chunks, float(group["weight_decay"]), float(group["momentum"]), float(group["lr"]),
                          group["momentum"] != 0, first, group["nesterov"], zero)
+        self._mark_written(ops, stepped, zero)
         return loss
 
 
@@ -438,12 +464,13 @@ class StatefulNativeMixin(NativeStepMixin):
                     continue
                 self._check_tensors(p, g)       # a tensor changed hands or moved: validate again (nothing is written in this pass)
                 items.append((gi, rec, (p, g, group, names)))
-        classes, counted = collections.OrderedDict(), []
+        classes, counted, stepped = collections.OrderedDict(), [], []
         if self.STEP_IS_TENSOR:
             self._sync_counts()
         for gi, rec, todo in items:
             if todo is not None:
                 rec = recs[id(todo[0])] = self._make_record(rec, *todo)
+            stepped.append(rec)
             if self.STEP_IS_TENSOR:
                 rec.val += 1
                 counted.append(rec)
@@ -457,6 +484,7 @@ class StatefulNativeMixin(NativeStepMixin):
         for key, rows in classes.items():
             tensors, chunks = self._tables_for(key[1], rows)
             self._launch(ops, self.param_groups[key[0]], key, tensors, chunks, zero)
+        self._mark_written(ops, stepped, zero)
         return loss
 
 

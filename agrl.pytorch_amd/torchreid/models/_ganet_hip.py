@@ -31,15 +31,15 @@ def _pack_entries(model, pack, dtype, s16):
         'qk_w': torch.cat([pam.query_conv.weight, pam.key_conv.weight], 0).detach().float().permute(0, 2, 3, 1).contiguous().to(dtype),
         'qk_b': torch.cat([pam.query_conv.bias, pam.key_conv.bias], 0).detach().float().contiguous(),
         'cq': pam.query_conv.weight.shape[0],
-        'v_w': pam.value_conv.weight.detach().float().view(pam.value_conv.weight.shape[0], -1).contiguous().to(dtype),
-        'v_b': pam.value_conv.bias.detach().float().contiguous(),
+        'v_w': R.own_copy(pam.value_conv.weight.detach().float().view(pam.value_conv.weight.shape[0], -1), dtype),
+        'v_b': R.own_copy(pam.value_conv.bias, torch.float32),
         'pam_gamma': float(pam.gamma.detach()),
         'bnneck': R.single_bnneck(model.bottleneck),
         'graph': [],
     })
     for layer in model.graph_layers:
         scale, shift = R.fold_bn1d(layer.bn)
-        pack['graph'].append({'w': layer.linear.weight.detach().to(dtype).contiguous(), 'scale': scale, 'shift': shift,
+        pack['graph'].append({'w': R.own_copy(layer.linear.weight, dtype), 'scale': scale, 'shift': shift,
                               'slope': float(layer.relu.negative_slope), 'use_pose': bool(layer.use_pose),
                               'learn_graph': bool(layer.learn_graph)})
 

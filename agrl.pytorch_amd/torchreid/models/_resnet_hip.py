@@ -8,7 +8,9 @@ Data layout in HBM
     conv weights  OHWI (Cout, R, S, Cin), eval BatchNorm folded in, compute dtype; bias fp32
 
 The packed weights are cached per (device, precision) and rebuilt when any parameter / buffer changed
-(data pointer or in-place version), unless ``model.hip_static_weights`` is set.
+(data pointer or in-place version), unless ``model.hip_static_weights`` is set. The library's own writers of these tensors -- the
+native optimiser steps, the train-mode BatchNorm -- bump the versions themselves (hip_ops.written); a pack entry never aliases a
+parameter (own_copy).
 """
 from __future__ import annotations
 
@@ -54,6 +56,13 @@ def fold_conv_bn(conv, bn, dtype, split16=False):
         assert dtype == torch.float32
         return ops.split16_inloop_weights(w), shift.contiguous()
     return w.to(dtype).contiguous(), shift.contiguous()
+
+
+def own_copy(param, dtype):
+    """A parameter as ``dtype`` for a pack, in memory of the pack's own. ``.to(dtype)`` and ``.contiguous()`` hand back the parameter's
+    storage where they have nothing to do (fp32 modes): a pack entry made with them alone follows a raw write of the parameter while
+    the folded entries beside it do not -- under ``hip_static_weights`` a forward on half-stepped weights."""
+    return param.detach().to(dtype, copy=True).contiguous()
 
 
 def fold_bn1d(bn):

@@ -30,7 +30,7 @@ def _pack_entries(model, pack, dtype, s16):
         if not isinstance(model.fc1[2], torch.nn.ReLU):
             raise NotImplementedError('the HIP head is Linear + BatchNorm1d + ReLU; fc1 ends in {}'.format(type(model.fc1[2]).__name__))
         scale, shift = R.fold_bn1d(model.fc1[1])
-        pack['fc'] = (model.fc1[0].weight.detach().to(dtype).contiguous(), scale, shift)
+        pack['fc'] = (R.own_copy(model.fc1[0].weight, dtype), scale, shift)
     else:
         pack['bnneck'] = R.single_bnneck(model.bottleneck)
 

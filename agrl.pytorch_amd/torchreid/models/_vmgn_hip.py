@@ -30,7 +30,7 @@ def _pack_entries(model, pack, dtype, s16):
     pack['graph'] = []
     for layer in model.graph_layers:
         scale, shift = R.fold_bn1d(layer.bn)
-        gw = layer.linear.weight.detach().to(dtype).contiguous()
+        gw = R.own_copy(layer.linear.weight, dtype)
         if s16 and whole_k_tiles(gw):
             # the GraphLayer's Linear in the split-fp16 arithmetic as well (182 -> ~70 us per layer at 32 tracklets): weight times
             # 2^k, the 2^-k folded into the BatchNorm scale the GEMM's epilogue multiplies the accumulator with (exact)

@@ -257,3 +257,39 @@ def test_native_route_groups_launches_by_step_count(monkeypatch):
     step()
     opt.load_state_dict(saved)                           # rewinds the counts
     assert step() == [(1, 4), (1, 11), (3, 6)] and counts() == [6.0, 4.0, 6.0, 11.0, 6.0]
+
+
+@pytest.mark.parametrize("kind", ["adam", "amsgrad", "sgd", "nesterov", "rmsprop", "adabound", "radam"])
+@pytest.mark.parametrize("zero", [False, True])
+def test_native_route_bumps_the_versions_of_what_it_wrote(kind, zero, monkeypatch):
+    """The kernels write through raw pointers; the step makes the writes visible to whatever is keyed on torch's version counters (the
+    eval forward's pack cache, autograd's saved tensors): +1 on every stepped parameter and state tensor, on the gradients only when
+    the step zero-filled them, nothing on a parameter that sat out. All seven names of init_optim_native, i.e. all five step
+    implementations (HipAdam, HipSGD, and StatefulNativeMixin's for HipRMSprop, HipAdaBound, HipRAdam). Launch and device tables stubbed,
+    as above."""
+    from torchreid import _hip
+    from torchreid import hip_ops as ops
+    launched = []
+    for name in ("rmsprop_step", "adabound_step", "radam_step"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name: launched.append(_n))
+    monkeypatch.setattr(hip_optim.NativeStepMixin, "_all_cpu", lambda self: False)
+    monkeypatch.setattr(hip_optim.NativeStepMixin, "_check_tensors", staticmethod(lambda p, g: None))
+    monkeypatch.setattr(hip_optim.NativeStepMixin, "_tables_for", lambda self, device, rows: (len(rows), None))
+    monkeypatch.setattr(_hip, "lib", lambda: None)
+    monkeypatch.setattr(ops, "adam_step", lambda *a: launched.append("adam_step"))
+    monkeypatch.setattr(ops, "sgd_step", lambda *a: launched.append("sgd_step"))
+    ps = _params(shapes=((8,),) * 3)
+    _set_grads(ps, 1)
+    ps[2].grad = None
+    opt = hip_optim.init_optim_native(kind, ps, 1e-3, 5e-4)
+    opt.step(zero_grads=zero)                            # creates the state
+    state = [t for p in ps[:2] for k, t in sorted(opt.state[p].items()) if k != "step"]
+    per_param = {"adam": 2, "amsgrad": 3, "sgd": 1, "nesterov": 1, "rmsprop": 2, "adabound": 2, "radam": 2}[kind]
+    assert len(state) == 2 * per_param and all(torch.is_tensor(t) for t in state) and ps[2] not in opt.state
+    want = {"amsgrad": "adam", "nesterov": "sgd"}.get(kind, kind) + "_step"
+    assert launched and set(launched) == {want}         # the native route ran, not a per-tensor torch rule
+    for _ in range(2):
+        before = [t._version for t in ps + state], [p.grad._version for p in ps[:2]]
+        opt.step(zero_grads=zero)
+        assert [t._version for t in ps + state] == [v + 1 for v in before[0][:2]] + [before[0][2]] + [v + 1 for v in before[0][3:]]
+        assert [p.grad._version for p in ps[:2]] == [v + (1 if zero else 0) for v in before[1]]
