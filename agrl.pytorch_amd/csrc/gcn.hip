@@ -84,6 +84,108 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ f, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Tiled Gram / pair product for any V (the slice forms above keep a whole V x 128 slice in LDS: V <= 304, two of them V <= 144).
+// grid = (tiles, B), 256 threads. A workgroup owns one 64 x 64 tile (ti, tj) of out[b] = a[b] b[b]^T and walks ALL C channels in
+// chunks of TG_CK = 64 staged in LDS (rows of TG_CK * 4 + 16 bytes, the padding of GRAM_ROWB), so the result is fully summed:
+// out is (B,V,V), i.e. the partial layout with nz = 1. Wave w owns rows [16 w, 16 w + 16) of the tile and its four 16 x 16
+// column fragments: four independent exact-fp32 MFMA chains.
+// Summation order of one output element, fixed: ONE fp32 accumulator from 0; chunks c0 ascending, inside a chunk the four
+// 16-channel steps ks ascending, inside a step the float4 component q = 0..3, and one v_mfma_f32_16x16x4_f32 adds the channels
+// c0 + 16 ks + q + 4 k, k = 0..3 ascending (an fp32 fma chain). The same order for (i, j) and (j, i).
+// Gram (PAIR = false): only the tiles ti <= tj are computed and every value is stored at (i, j) AND (j, i) -- in a diagonal
+// tile from its i <= j half -- so the matrix is bit-symmetric by construction and g_ii exists once. Every element of out is
+// written exactly once.
+constexpr int TG_T = 64;
+constexpr int TG_CK = 64;
+constexpr int TG_ROWB = TG_CK * 4 + 16;
+
+template <bool PAIR>
+__global__ __launch_bounds__(256) void gram_tiled_kernel(const float* __restrict__ a, const float* __restrict__ b2,
+                                                         float* __restrict__ out, int V, int C, int T) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_t[2 * TG_T * TG_ROWB];
+    const int bz = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int ti, tj;
+    if (PAIR) {
+        ti = blockIdx.x / T;
+        tj = blockIdx.x - ti * T;
+    } else {  // upper triangle, row by row: T tiles of row 0, T - 1 of row 1, ..
+        int rem = blockIdx.x;
+        ti = 0;
+        while (rem >= T - ti) { rem -= T - ti; ++ti; }
+        tj = ti + rem;
+    }
+    const bool diag = !PAIR && ti == tj;
+    const float* pa = a + (size_t)bz * V * C;
+    const float* pb = (PAIR ? b2 : a) + (size_t)bz * V * C;
+    unsigned char* sA = s_t;
+    unsigned char* sB = diag ? s_t : s_t + TG_T * TG_ROWB;   // a diagonal Gram tile multiplies its row block with itself
+    const int srow = tid >> 4, scol = tid & 15;               // stage: thread -> float4 scol of rows srow + 16 i
+    const int frow = lane & 15, fch = lane >> 4;
+    f32x4_t acc[4];
+#pragma unroll
+    for (int fj = 0; fj < 4; ++fj) acc[fj] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < C; c0 += TG_CK) {
+        float4 va[4], vb[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = srow + 16 * i;
+            const int ga = ti * TG_T + r, gb = tj * TG_T + r;
+            va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            vb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ga < V) va[i] = *reinterpret_cast<const float4*>(pa + (size_t)ga * C + c0 + scol * 4);
+            if (!diag && gb < V) vb[i] = *reinterpret_cast<const float4*>(pb + (size_t)gb * C + c0 + scol * 4);
+        }
+        __syncthreads();   // the previous chunk's fragment reads are done
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = srow + 16 * i;
+            *reinterpret_cast<float4*>(sA + r * TG_ROWB + scol * 16) = va[i];
+            if (!diag) *reinterpret_cast<float4*>(sB + r * TG_ROWB + scol * 16) = vb[i];
+        }
+        __syncthreads();
+        const unsigned char* qa = sA + (wave * 16 + frow) * TG_ROWB + fch * 16;
+        const unsigned char* qb = sB + frow * TG_ROWB + fch * 16;
+#pragma unroll
+        for (int ks = 0; ks < TG_CK / 16; ++ks) {
+            const float4 av = *reinterpret_cast<const float4*>(qa + ks * 64);
+            float4 bv[4];
+#pragma unroll
+            for (int fj = 0; fj < 4; ++fj) bv[fj] = *reinterpret_cast<const float4*>(qb + fj * 16 * TG_ROWB + ks * 64);
+#pragma unroll
+            for (int fj = 0; fj < 4; ++fj) acc[fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv[fj].x, acc[fj], 0, 0, 0);
+#pragma unroll
+            for (int fj = 0; fj < 4; ++fj) acc[fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv[fj].y, acc[fj], 0, 0, 0);
+#pragma unroll
+            for (int fj = 0; fj < 4; ++fj) acc[fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv[fj].z, acc[fj], 0, 0, 0);
+#pragma unroll
+            for (int fj = 0; fj < 4; ++fj) acc[fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv[fj].w, acc[fj], 0, 0, 0);
+        }
+    }
+    // D[row = 4 * (lane >> 4) + r][col = lane & 15]
+    float* dst = out + (size_t)bz * V * V;
+#pragma unroll
+    for (int fj = 0; fj < 4; ++fj) {
+        const int j = tj * TG_T + fj * 16 + frow;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = ti * TG_T + wave * 16 + fch * 4 + r;
+            if (i >= V || j >= V) continue;
+            const float v = acc[fj][r];
+            if (PAIR) {
+                dst[(size_t)i * V + j] = v;
+            } else if (!diag) {
+                dst[(size_t)i * V + j] = v;
+                dst[(size_t)j * V + i] = v;
+            } else if (i <= j) {
+                dst[(size_t)i * V + j] = v;
+                if (i < j) dst[(size_t)j * V + i] = v;
+            }
+        }
+    }
+}
+
 // sum of the nz Gram partials of one element, z ascending (fixed order); sixteen loads in flight at a time instead of a
 // load -> add chain (nz = 16 for C = 2048: one batch)
 __device__ inline float zsum(const float* p, int nz, int zstride) {
@@ -165,6 +267,69 @@ __global__ __launch_bounds__(256) void graph_finalize_kernel(const float* __rest
             }
             G[((size_t)b * V + i) * V + j] = g;
         }
+    }
+}
+
+constexpr int FINALIZE_RESIDENT_MAX_V = 256;   // graph_finalize_kernel: JPL = 4 columns per lane
+
+// zsum for images whose z stride V * V may pass 2^31: the same additions, from 0, z ascending
+__device__ inline float zsum_wide(const float* p, int nz, size_t zstride) {
+    float s = 0.f;
+    for (int z = 0; z < nz; ++z) s += p[(size_t)z * zstride];
+    return s;
+}
+
+// Finalize for V > 256 (graph_finalize_kernel holds a row's columns in four registers per lane): the same arithmetic stage by
+// stage, rows streamed from HBM in two passes. grid = (ceil(V / 4), B), 256 threads: one wavefront per graph row i.
+//   pass 1  lane's columns j = lane, lane + 64, .. ascending: sim_ij (and |adj_ij|) added into the lane's sum, then the wave sum --
+//           the summation shape of graph_finalize_kernel;
+//   pass 2  sim_ij formed again by the same instructions (bitwise the value that was summed), normalised, mixed, stored.
+// The squared norms n_j are read where they lie, on the diagonal of the Gram (V lines per tracklet: cache-resident), summed
+// over the nz partials by the same z-ascending chain as every other entry, so D2_ii = (n_i + n_i) - 2 g_ii is exactly 0.
+// Nothing is kept in LDS: V is bounded by memory only. All indices are size_t.
+__global__ __launch_bounds__(256) void graph_finalize_rows_kernel(const float* __restrict__ gram_part, int nz,
+                                                                  const float* __restrict__ adj, const uint32_t* __restrict__ adj_bits,
+                                                                  float* __restrict__ G, int V, int use_pose, int learn_graph, int mask_diag) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= V) return;
+    const size_t vv = (size_t)V * V;
+    const float* gp = learn_graph ? gram_part + (size_t)b * nz * vv : nullptr;
+    const size_t row = (size_t)b * V + i;
+    const float ni = learn_graph ? zsum_wide(gp + (size_t)i * V + i, nz, vv) : 0.f;
+    auto sim_at = [&](int j) {
+        const float g = zsum_wide(gp + (size_t)i * V + j, nz, vv);
+        const float nj = zsum_wide(gp + (size_t)j * V + j, nz, vv);
+        // similarity: 2 / (exp(sqrt(clamp(n_j + n_i - 2 g_ij, 1e-12))) + 1)
+        float d2 = (nj + ni) - 2.f * g;
+        d2 = fmaxf(d2, 1e-12f);
+        float s = 2.f / (expf(sqrtf(d2)) + 1.f);
+        if (mask_diag && j == i) s = 0.f;
+        return s;
+    };
+    auto pose_at = [&](int j) {
+        float a = adj_at(adj, adj_bits, row, V, j);
+        if (mask_diag && j == i) a = 0.f;
+        return a;
+    };
+    float ssum = 0.f, asum = 0.f;
+    for (int j = lane; j < V; j += 64) {
+        if (learn_graph) ssum += fabsf(sim_at(j));
+        if (use_pose) asum += fabsf(pose_at(j));
+    }
+    ssum = wave_sum(ssum);
+    asum = wave_sum(asum);
+    const float sden = fmaxf(ssum, 1e-12f), aden = fmaxf(asum, 1e-12f);
+    for (int j = lane; j < V; j += 64) {
+        float g;
+        if (learn_graph) {
+            g = sim_at(j) / sden;
+            if (use_pose) g = (pose_at(j) / aden + g) / 2.f;
+        } else {
+            g = pose_at(j) / aden;
+        }
+        G[row * V + j] = g;
     }
 }
 
@@ -288,6 +453,61 @@ __global__ __launch_bounds__(PROP_THREADS) void graph_propagate_tiled_kernel(
             acc[4 * k4 + 1] = fmaf(g4.y, hv, acc[4 * k4 + 1]);
             acc[4 * k4 + 2] = fmaf(g4.z, hv, acc[4 * k4 + 2]);
             acc[4 * k4 + 3] = fmaf(g4.w, hv, acc[4 * k4 + 3]);
+        }
+    }
+    const float sc = bn_scale[cc], sh = bn_shift[cc];
+#pragma unroll
+    for (int k = 0; k < PROPT_ROWS; ++k) {
+        const int v = v0 + k;
+        if (v < V && live) {
+            const size_t idx = ((size_t)b * V + v) * C + c;
+            float y = fmaf(acc[k], sc, sh);
+            y = y > 0.f ? y : slope * y;
+            const float o = one_minus_gamma * f[idx] + gamma * y;
+            out[idx] = o;
+            if (out_lp) out_lp[idx] = f32_to_lp16(o);
+        }
+    }
+}
+
+// The tiled form beyond V = 1024 (its 16 x V graph rows pass 64 KB of LDS): the same grid and the same thread -> output map,
+// the u dimension staged through LDS in chunks of PROPC_U graph columns. One running fp32 accumulator per output, fmaf chain
+// from 0 with u ascending inside a chunk and chunks ascending: bit for bit the order of graph_propagate_tiled_kernel.
+constexpr int PROPC_U = 512;
+__global__ __launch_bounds__(PROP_THREADS) void graph_propagate_chunked_kernel(
+    const float* __restrict__ f, const float* __restrict__ h, const float* __restrict__ G,
+    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, float one_minus_gamma, float gamma,
+    float slope, float* __restrict__ out, lp16_t* __restrict__ out_lp, int V, int C) {
+    __shared__ __attribute__((aligned(16))) float s_gr[PROPC_U * PROPT_ROWS];   // s_gr[u * 16 + k] = G[v0 + k][u0 + u]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int c = blockIdx.y * PROP_THREADS + tid;
+    const bool live = c < C;
+    const int cc = live ? c : C - 1;
+    const int v0 = blockIdx.z * PROPT_ROWS;
+    const float* Gb = G + (size_t)b * V * V;
+    const float* hb = h + (size_t)b * V * C + cc;
+    float acc[PROPT_ROWS];
+#pragma unroll
+    for (int k = 0; k < PROPT_ROWS; ++k) acc[k] = 0.f;
+    for (int u0 = 0; u0 < V; u0 += PROPC_U) {
+        const int nu = min(PROPC_U, V - u0);
+        __syncthreads();   // the previous chunk has been consumed
+        for (int e = tid; e < nu * PROPT_ROWS; e += PROP_THREADS) {
+            const int k = e / nu, u = e - k * nu;     // coalesced over u along a graph row
+            s_gr[u * PROPT_ROWS + k] = v0 + k < V ? Gb[(size_t)(v0 + k) * V + u0 + u] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int u = 0; u < nu; ++u) {
+            const float hv = hb[(size_t)(u0 + u) * C];
+#pragma unroll
+            for (int k4 = 0; k4 < PROPT_ROWS / 4; ++k4) {
+                const float4 g4 = *reinterpret_cast<const float4*>(&s_gr[u * PROPT_ROWS + 4 * k4]);
+                acc[4 * k4 + 0] = fmaf(g4.x, hv, acc[4 * k4 + 0]);
+                acc[4 * k4 + 1] = fmaf(g4.y, hv, acc[4 * k4 + 1]);
+                acc[4 * k4 + 2] = fmaf(g4.z, hv, acc[4 * k4 + 2]);
+                acc[4 * k4 + 3] = fmaf(g4.w, hv, acc[4 * k4 + 3]);
+            }
         }
     }
     const float sc = bn_scale[cc], sh = bn_shift[cc];
@@ -876,11 +1096,11 @@ __global__ __launch_bounds__(64 * GT_WAVES) void graph_tracklet_kernel(const flo
 __global__ __launch_bounds__(256) void pose_adjacency_kernel(const float* __restrict__ poses, const unsigned char* __restrict__ detected,
                                                              float* __restrict__ adj, uint32_t* __restrict__ adj_bits, int S, int num_split, int levels,
                                                              int pyramid, int P, double height, float threshold) {
-    __shared__ unsigned s_mask[3 * 64];  // [frame][part] node bitmask (P <= 31), S <= 64
+    extern __shared__ unsigned s_mask[];  // [frame][part] node bitmask (P <= 31): 3 S words of dynamic LDS
     const int b = blockIdx.x, tid = threadIdx.x;
     const int V = S * P;
-    if (tid < 3 * S) {
-        const int t = tid / 3, part = tid - 3 * t;
+    for (int m = tid; m < 3 * S; m += 256) {
+        const int t = m / 3, part = m - 3 * t;
         unsigned mask = 0;
         if (detected[(size_t)b * S + t]) {
             // keypoint groups of the reference: head {0,1,14,15,16,17}, body {2..7}, leg {8..13}
@@ -913,7 +1133,7 @@ __global__ __launch_bounds__(256) void pose_adjacency_kernel(const float* __rest
                 }
             }
         }
-        s_mask[tid] = mask;
+        s_mask[m] = mask;
     }
     __syncthreads();
     auto edge = [&](int i, int j) {
@@ -926,18 +1146,21 @@ __global__ __launch_bounds__(256) void pose_adjacency_kernel(const float* __rest
         }
         return on;
     };
+    // the tracklet's entries are dealt out over the gridDim.y workgroups of the tracklet (1 for S <= 64), each of which built
+    // the masks for itself
+    const size_t first = (size_t)blockIdx.y * 256 + tid, stride = (size_t)gridDim.y * 256;
     if (adj) {
         float* ab = adj + (size_t)b * V * V;
-        for (int e = tid; e < V * V; e += 256) {
-            const int i = e / V, j = e - i * V;
+        for (size_t e = first; e < (size_t)V * V; e += stride) {
+            const int i = (int)(e / V), j = (int)(e - (size_t)i * V);
             ab[e] = edge(i, j) ? 1.f : 0.f;
         }
     }
     if (adj_bits) {   // bit j & 31 of word j >> 5 of row i: 56 x 56 nodes = 448 bytes instead of 12.5 KB
         const int W = (V + 31) >> 5;
         uint32_t* bb = adj_bits + (size_t)b * V * W;
-        for (int e = tid; e < V * W; e += 256) {
-            const int i = e / W, w = e - i * W;
+        for (size_t e = first; e < (size_t)V * W; e += stride) {
+            const int i = (int)(e / W), w = (int)(e - (size_t)i * W);
             uint32_t word = 0;
             for (int q = 0; q < 32; ++q) {
                 const int j = 32 * w + q;
@@ -972,7 +1195,13 @@ extern "C" int agrl_graph_gram(const float* f, float* gram_part, int B, int V, i
     AGRL_CHECK_ARG(cslice == GRAM_CS && C % GRAM_CS == 0, "agrl_graph_gram: cslice must be %d and divide C", GRAM_CS);
     const int Vp = (V + 15) & ~15;
     const size_t lds = (size_t)Vp * GRAM_ROWB;
-    AGRL_CHECK_ARG(lds <= 160 * 1024, "agrl_graph_gram: V=%d too large", V);
+    if (lds > 160 * 1024) {   // V > 304: 64 x 64 tiles, fully summed over C -- gram_part is (B, 1, V, V); any V
+        const long long T = cdiv(V, TG_T), tiles = T * (T + 1) / 2;
+        AGRL_CHECK_ARG(tiles <= 0x7fffffffLL && B <= 65535, "agrl_graph_gram: V=%d B=%d exceed the launch grid", V, B);
+        hipLaunchKernelGGL(gram_tiled_kernel<false>, dim3((unsigned)tiles, B), dim3(256), 0, (hipStream_t)stream, f, (const float*)nullptr, gram_part, V, C, (int)T);
+        AGRL_CHECK_LAUNCH("agrl_graph_gram");
+        return 0;
+    }
     const int nz = C / GRAM_CS;
     if (lds > 64 * 1024) {  // V >= 125 (e.g. seq_len 20 x 7 parts): above the default dynamic-LDS limit of a launch
         hipError_t e = hipFuncSetAttribute((const void*)gram_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -984,11 +1213,18 @@ extern "C" int agrl_graph_gram(const float* f, float* gram_part, int B, int V, i
 }
 
 extern "C" int agrl_graph_pair_product(const float* a, const float* b, float* part, float* out, int B, int V, int C, agrl_stream_t stream) {
-    AGRL_CHECK_ARG(a && b && part && out, "agrl_graph_pair_product: null pointer");
+    AGRL_CHECK_ARG(a && b && out, "agrl_graph_pair_product: null pointer");
     AGRL_CHECK_ARG(B > 0 && V > 0 && C > 0 && C % GRAM_CS == 0, "agrl_graph_pair_product: bad shape (C must be a multiple of %d)", GRAM_CS);
     const int Vp = (V + 15) & ~15;
     const size_t lds = (size_t)2 * Vp * GRAM_ROWB;
-    AGRL_CHECK_ARG(lds <= 160 * 1024, "agrl_graph_pair_product: V=%d too large (two V x 128 slices must fit the LDS)", V);
+    if (lds > 160 * 1024) {   // V > 144: all 64 x 64 tiles, fully summed over C straight into out; part is not used; any V
+        const long long T = cdiv(V, TG_T), tiles = T * T;
+        AGRL_CHECK_ARG(tiles <= 0x7fffffffLL && B <= 65535, "agrl_graph_pair_product: V=%d B=%d exceed the launch grid", V, B);
+        hipLaunchKernelGGL(gram_tiled_kernel<true>, dim3((unsigned)tiles, B), dim3(256), 0, (hipStream_t)stream, a, b, out, V, C, (int)T);
+        AGRL_CHECK_LAUNCH("agrl_graph_pair_product");
+        return 0;
+    }
+    AGRL_CHECK_ARG(part, "agrl_graph_pair_product: null pointer");
     const int nz = C / GRAM_CS;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)gram_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1008,7 +1244,13 @@ extern "C" int agrl_graph_finalize(const float* gram_part, int nz, const float* 
     AGRL_CHECK_ARG(use_pose || learn_graph, "agrl_graph_finalize: use_pose or learn_graph must be set");
     AGRL_CHECK_ARG(!use_pose || adj, "agrl_graph_finalize: use_pose needs adj");
     AGRL_CHECK_ARG(!learn_graph || (gram_part && nz > 0), "agrl_graph_finalize: learn_graph needs the Gram partials");
-    AGRL_CHECK_ARG(V <= 256, "agrl_graph_finalize: V=%d > 256 not supported", V);
+    if (V > FINALIZE_RESIDENT_MAX_V) {   // rows streamed from HBM, any V
+        AGRL_CHECK_ARG(B <= 65535, "agrl_graph_finalize: B=%d > 65535 tracklets at V > %d", B, FINALIZE_RESIDENT_MAX_V);
+        hipLaunchKernelGGL(graph_finalize_rows_kernel, dim3(cdiv(V, 4), B), dim3(256), 0, (hipStream_t)stream, gram_part, nz, adj,
+                           (const uint32_t*)nullptr, G, V, use_pose, learn_graph, mask_diag);
+        AGRL_CHECK_LAUNCH("agrl_graph_finalize");
+        return 0;
+    }
     hipLaunchKernelGGL(graph_finalize_kernel, dim3(B, cdiv(V, 4)), dim3(256), (size_t)V * sizeof(float),
                        (hipStream_t)stream, gram_part, nz, adj, (const uint32_t*)nullptr, G, V, use_pose, learn_graph, mask_diag);
     AGRL_CHECK_LAUNCH("agrl_graph_finalize");
@@ -1021,7 +1263,13 @@ extern "C" int agrl_graph_finalize_bits(const float* gram_part, int nz, const ui
     AGRL_CHECK_ARG(use_pose || learn_graph, "agrl_graph_finalize_bits: use_pose or learn_graph must be set");
     AGRL_CHECK_ARG(!use_pose || adj_bits, "agrl_graph_finalize_bits: use_pose needs the packed adjacency");
     AGRL_CHECK_ARG(!learn_graph || (gram_part && nz > 0), "agrl_graph_finalize_bits: learn_graph needs the Gram partials");
-    AGRL_CHECK_ARG(V <= 256, "agrl_graph_finalize_bits: V=%d > 256 not supported", V);
+    if (V > FINALIZE_RESIDENT_MAX_V) {
+        AGRL_CHECK_ARG(B <= 65535, "agrl_graph_finalize_bits: B=%d > 65535 tracklets at V > %d", B, FINALIZE_RESIDENT_MAX_V);
+        hipLaunchKernelGGL(graph_finalize_rows_kernel, dim3(cdiv(V, 4), B), dim3(256), 0, (hipStream_t)stream, gram_part, nz,
+                           (const float*)nullptr, adj_bits, G, V, use_pose, learn_graph, mask_diag);
+        AGRL_CHECK_LAUNCH("agrl_graph_finalize_bits");
+        return 0;
+    }
     hipLaunchKernelGGL(graph_finalize_kernel, dim3(B, cdiv(V, 4)), dim3(256), (size_t)V * sizeof(float),
                        (hipStream_t)stream, gram_part, nz, (const float*)nullptr, adj_bits, G, V, use_pose, learn_graph, mask_diag);
     AGRL_CHECK_LAUNCH("agrl_graph_finalize_bits");
@@ -1151,7 +1399,13 @@ extern "C" int agrl_graph_propagate(const float* f, const float* h, const float*
     const bool fixed = false;  // register-resident h (VT > 0) spills: hipcc hoists every LDS graph read; keep h in LDS
     const size_t lds = ((size_t)V * Vp + (fixed ? 0 : (size_t)V * PROP_THREADS)) * sizeof(float);
     if (lds > 160 * 1024) {   // graph + h slab no longer fit the LDS (V > ~125): 16 graph rows per workgroup, h streamed from L2
-        AGRL_CHECK_ARG((size_t)V * PROPT_ROWS * 4 <= 64 * 1024, "agrl_graph_propagate: V=%d too large", V);
+        if ((size_t)V * PROPT_ROWS * 4 > 64 * 1024) {   // V > 1024: the 16 graph rows go through LDS in chunks, any V
+            AGRL_CHECK_ARG(cdiv(V, PROPT_ROWS) <= 65535 && cdiv(C, PROP_THREADS) <= 65535, "agrl_graph_propagate: V=%d C=%d exceed the launch grid", V, C);
+            hipLaunchKernelGGL(graph_propagate_chunked_kernel, dim3(B, cdiv(C, PROP_THREADS), cdiv(V, PROPT_ROWS)), dim3(PROP_THREADS),
+                               0, (hipStream_t)stream, f, h, G, bn_scale, bn_shift, keep, gamma, slope, out, (lp16_t*)out_lp, V, C);
+            AGRL_CHECK_LAUNCH("agrl_graph_propagate");
+            return 0;
+        }
         hipLaunchKernelGGL(graph_propagate_tiled_kernel, dim3(B, cdiv(C, PROP_THREADS), cdiv(V, PROPT_ROWS)), dim3(PROP_THREADS),
                            (size_t)V * PROPT_ROWS * 4, (hipStream_t)stream, f, h, G, bn_scale, bn_shift, keep, gamma, slope, out, (lp16_t*)out_lp, V, C);
         AGRL_CHECK_LAUNCH("agrl_graph_propagate");
@@ -1177,17 +1431,28 @@ extern "C" int agrl_graph_propagate(const float* f, const float* h, const float*
 }
 
 
+// the per-frame masks live in dynamic LDS: 3 S words within the 64 KB every launch may ask for
+constexpr int POSE_MAX_S = 64 * 1024 / 12;
+// workgroups per tracklet: one up to S = 64 frames (the launch shape the kernel always had), beyond that one per 16 K entries of
+// the V x V image, at most 1024 (each rebuilds the 3 S masks: cheap next to its share of the image)
+static unsigned pose_slices(int S, int P) {
+    if (S <= 64) return 1;
+    const size_t vv = (size_t)S * P * S * P;
+    const size_t n = (vv + 16383) / 16384;
+    return (unsigned)(n < 1024 ? n : 1024);
+}
+
 extern "C" int agrl_pose_adjacency(const float* poses, const unsigned char* detected, float* adj, int B, int S, int num_split,
                                    int pyramid_part, float height, float threshold, agrl_stream_t stream) {
     AGRL_CHECK_ARG(poses && detected && adj, "agrl_pose_adjacency: null pointer");
-    AGRL_CHECK_ARG(B > 0 && S > 0 && S <= 64, "agrl_pose_adjacency: 1 <= S <= 64 frames (got %d)", S);
+    AGRL_CHECK_ARG(B > 0 && S > 0 && S <= POSE_MAX_S, "agrl_pose_adjacency: 1 <= S <= %d frames (got %d)", POSE_MAX_S, S);
     AGRL_CHECK_ARG(num_split >= 1 && num_split <= 16 && (num_split & (num_split - 1)) == 0,
                    "agrl_pose_adjacency: num_split must be a power of two <= 16 (got %d)", num_split);
     int levels = 0;
     while ((1 << levels) < num_split) ++levels;
     const int P = pyramid_part ? 2 * num_split - 1 : num_split;
-    hipLaunchKernelGGL(pose_adjacency_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, poses, detected, adj, (uint32_t*)nullptr, S, num_split,
-                       levels, pyramid_part ? 1 : 0, P, (double)height, threshold);
+    hipLaunchKernelGGL(pose_adjacency_kernel, dim3(B, pose_slices(S, P)), dim3(256), (size_t)3 * S * sizeof(unsigned), (hipStream_t)stream, poses, detected,
+                       adj, (uint32_t*)nullptr, S, num_split, levels, pyramid_part ? 1 : 0, P, (double)height, threshold);
     AGRL_CHECK_LAUNCH("agrl_pose_adjacency");
     return 0;
 }
@@ -1195,14 +1460,14 @@ extern "C" int agrl_pose_adjacency(const float* poses, const unsigned char* dete
 extern "C" int agrl_pose_adjacency_bits(const float* poses, const unsigned char* detected, uint32_t* adj_bits, int B, int S, int num_split,
                                         int pyramid_part, float height, float threshold, agrl_stream_t stream) {
     AGRL_CHECK_ARG(poses && detected && adj_bits, "agrl_pose_adjacency_bits: null pointer");
-    AGRL_CHECK_ARG(B > 0 && S > 0 && S <= 64, "agrl_pose_adjacency_bits: 1 <= S <= 64 frames (got %d)", S);
+    AGRL_CHECK_ARG(B > 0 && S > 0 && S <= POSE_MAX_S, "agrl_pose_adjacency_bits: 1 <= S <= %d frames (got %d)", POSE_MAX_S, S);
     AGRL_CHECK_ARG(num_split >= 1 && num_split <= 16 && (num_split & (num_split - 1)) == 0,
                    "agrl_pose_adjacency_bits: num_split must be a power of two <= 16 (got %d)", num_split);
     int levels = 0;
     while ((1 << levels) < num_split) ++levels;
     const int P = pyramid_part ? 2 * num_split - 1 : num_split;
-    hipLaunchKernelGGL(pose_adjacency_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, poses, detected, (float*)nullptr, adj_bits, S, num_split,
-                       levels, pyramid_part ? 1 : 0, P, (double)height, threshold);
+    hipLaunchKernelGGL(pose_adjacency_kernel, dim3(B, pose_slices(S, P)), dim3(256), (size_t)3 * S * sizeof(unsigned), (hipStream_t)stream, poses, detected,
+                       (float*)nullptr, adj_bits, S, num_split, levels, pyramid_part ? 1 : 0, P, (double)height, threshold);
     AGRL_CHECK_LAUNCH("agrl_pose_adjacency_bits");
     return 0;
 }

@@ -174,6 +174,94 @@ __global__ __launch_bounds__(256) void graph_matrix_backward_kernel(const float*
     }
 }
 
+// The same backward for any V, as three passes over V x V images in HBM (the kernel above keeps three of them in LDS: V <= 115).
+// Same formulas, same conventions (E_ii = 0, E_ij = 0 where D2_ij sits at the clamp), same reduction shape: r_i, c_i and the row
+// sums of T are a lane's terms j = lane, lane + 64, .. added ascending from 0, then the wave sum. All indices are size_t.
+//   1  graph_matrix_backward_rows_kernel    grid (ceil(V / 4), B), one wavefront per row i: S_ij is formed from the Gram
+//      (nz partials added z ascending, norms read on its diagonal) three times by the same instructions -- for r_i, for c_i, for
+//      E_ij -- instead of being kept; E -> M (the output is the only scratch: no workspace)
+//   2  graph_matrix_symmetrize_kernel       grid (tile pairs ti <= tj, B): T_ij = E_ij + E_ji in place -- one workgroup owns the
+//      64 x 64 tiles (ti, tj) and (tj, ti), reads both into LDS, then overwrites both
+//   3  graph_matrix_backward_finish_kernel  grid (ceil(V / 4), B), one wavefront per row: t_i = sum_j T_ij, then
+//      M_ij = 2 ((i == j ? t_i : 0) - T_ij) in place (each lane rewrites the elements it read)
+__device__ inline float gmb_zsum(const float* p, int nz, size_t zstride) {
+    float s = 0.f;
+    for (int z = 0; z < nz; ++z) s += p[(size_t)z * zstride];
+    return s;
+}
+
+__global__ __launch_bounds__(256) void graph_matrix_backward_rows_kernel(const float* __restrict__ gram_part, int nz,
+                                                                         const float* __restrict__ dG, float* __restrict__ E, int V,
+                                                                         int use_pose, int mask_diag) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= V) return;
+    const size_t vv = (size_t)V * V;
+    const float* gp = gram_part + (size_t)b * nz * vv;
+    const size_t row = ((size_t)b * V + i) * V;
+    const float half = use_pose ? 0.5f : 1.f;
+    const float ni = gmb_zsum(gp + (size_t)i * V + i, nz, vv);
+    // S_ij, and D_ij or 0 where the entry passes no gradient (the diagonal, clamped distances)
+    auto entry = [&](int j, float& d_live) {
+        const float g = gmb_zsum(gp + (size_t)i * V + j, nz, vv);
+        const float nj = gmb_zsum(gp + (size_t)j * V + j, nz, vv);
+        const float d2 = fmaxf((nj + ni) - 2.f * g, 1e-12f);
+        const float d = sqrtf(d2);
+        float sv = 2.f / (expf(d) + 1.f);
+        if (mask_diag && i == j) sv = 0.f;
+        d_live = (i == j || !(d2 > 1e-12f)) ? 0.f : d;
+        return sv;
+    };
+    float dl;
+    float r = 0.f;
+    for (int j = lane; j < V; j += 64) r += fabsf(entry(j, dl));
+    r = wave_sum(r);
+    const float den = fmaxf(r, 1e-12f);
+    float cdot = 0.f;
+    for (int j = lane; j < V; j += 64) cdot = fmaf(dG[row + j] * half, entry(j, dl) / den, cdot);
+    cdot = wave_sum(cdot);
+    for (int j = lane; j < V; j += 64) {
+        const float sv = entry(j, dl);
+        const float dS = r > 1e-12f ? (dG[row + j] * half - cdot) / den : 0.f;
+        const float dD = -sv * (1.f - 0.5f * sv) * dS;
+        E[row + j] = dl > 0.f ? dD / (2.f * dl) : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void graph_matrix_symmetrize_kernel(float* __restrict__ M, int V, int T) {
+    __shared__ float s_a[64][65];   // tile (ti, tj) of E: s_a[rr][c] = E[ti 64 + rr][tj 64 + c]
+    __shared__ float s_b[64][65];   // tile (tj, ti) of E: s_b[rr][c] = E[tj 64 + rr][ti 64 + c]
+    int rem = blockIdx.x, ti = 0;   // the pairs ti <= tj, row by row
+    while (rem >= T - ti) { rem -= T - ti; ++ti; }
+    const int tj = ti + rem;
+    const int c = threadIdx.x & 63, r0 = threadIdx.x >> 6;
+    float* Mb = M + (size_t)blockIdx.y * V * V;
+    for (int rr = r0; rr < 64; rr += 4) {
+        const int ai = ti * 64 + rr, aj = tj * 64 + c, bi = tj * 64 + rr, bj = ti * 64 + c;
+        s_a[rr][c] = (ai < V && aj < V) ? Mb[(size_t)ai * V + aj] : 0.f;
+        s_b[rr][c] = (bi < V && bj < V) ? Mb[(size_t)bi * V + bj] : 0.f;
+    }
+    __syncthreads();   // both tiles are in LDS: no other workgroup reads or writes them, so they can be overwritten
+    for (int rr = r0; rr < 64; rr += 4) {
+        const int ai = ti * 64 + rr, aj = tj * 64 + c, bi = tj * 64 + rr, bj = ti * 64 + c;
+        if (ai < V && aj < V) Mb[(size_t)ai * V + aj] = s_a[rr][c] + s_b[c][rr];              // E_ij + E_ji
+        if (ti != tj && bi < V && bj < V) Mb[(size_t)bi * V + bj] = s_b[rr][c] + s_a[c][rr];
+    }
+}
+
+__global__ __launch_bounds__(256) void graph_matrix_backward_finish_kernel(float* __restrict__ M, int V) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= V) return;
+    float* Mi = M + ((size_t)b * V + i) * V;
+    float t = 0.f;
+    for (int j = lane; j < V; j += 64) t += Mi[j];
+    t = wave_sum(t);
+    for (int j = lane; j < V; j += 64) Mi[j] = 2.f * ((i == j ? t : 0.f) - Mi[j]);
+}
+
 // label-smoothed cross entropy: loss = sum_k mean_i(-q_ik log p_ik), q = (1 - eps) onehot + eps / K; dlogits = (p - q) / n.
 // grid = n rows (one workgroup per sample) + a finishing pass that adds the row losses in row order.
 __global__ __launch_bounds__(256) void xent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targets, int K,
@@ -274,7 +362,18 @@ extern "C" int agrl_graph_matrix_backward(const float* gram_part, int nz, const 
                                           int mask_diag, agrl_stream_t stream) {
     AGRL_CHECK_ARG(gram_part && dG && M && nz > 0 && B > 0 && V > 0, "agrl_graph_matrix_backward: bad arguments");
     const size_t lds = ((size_t)3 * V * V + V) * sizeof(float);
-    AGRL_CHECK_ARG(lds <= 160 * 1024, "agrl_graph_matrix_backward: V=%d too large (V <= 115)", V);
+    if (lds > 160 * 1024) {   // V > 116: three passes over the V x V image in HBM, M itself is the scratch; any V
+        AGRL_CHECK_ARG(B <= 65535, "agrl_graph_matrix_backward: B=%d > 65535 tracklets at V=%d", B, V);
+        const long long T = cdiv(V, 64), pairs = T * (T + 1) / 2;
+        AGRL_CHECK_ARG(pairs <= 0x7fffffffLL, "agrl_graph_matrix_backward: V=%d exceeds the launch grid", V);
+        hipLaunchKernelGGL(graph_matrix_backward_rows_kernel, dim3(cdiv(V, 4), B), dim3(256), 0, (hipStream_t)stream, gram_part, nz, dG, M, V, use_pose, mask_diag);
+        AGRL_CHECK_LAUNCH("agrl_graph_matrix_backward(rows)");
+        hipLaunchKernelGGL(graph_matrix_symmetrize_kernel, dim3((unsigned)pairs, B), dim3(256), 0, (hipStream_t)stream, M, V, (int)T);
+        AGRL_CHECK_LAUNCH("agrl_graph_matrix_backward(symmetrize)");
+        hipLaunchKernelGGL(graph_matrix_backward_finish_kernel, dim3(cdiv(V, 4), B), dim3(256), 0, (hipStream_t)stream, M, V);
+        AGRL_CHECK_LAUNCH("agrl_graph_matrix_backward(finish)");
+        return 0;
+    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)graph_matrix_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         AGRL_CHECK_ARG(e == hipSuccess, "agrl_graph_matrix_backward: cannot raise dynamic LDS: %s", hipGetErrorString(e));

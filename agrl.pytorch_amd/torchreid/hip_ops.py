@@ -1852,6 +1852,50 @@ def part_pool(x4_1, x4_2, splits, want_lp):
 
 GRAM_CSLICE = 128
 
+# The node counts V = parts x frames at which the GraphLayer's stages change kernel form (csrc/gcn.hip, csrc/train_tail.hip): up to
+# each limit a tracklet's operands sit in one workgroup's LDS / registers, beyond it they are tiled or streamed from HBM.
+GRAM_SLICE_MAX_V = 304          # agrl_graph_gram: a V x 128 fp32 slice (rows padded by 16 bytes, V rounded up to 16) in 160 KB
+FINALIZE_RESIDENT_MAX_V = 256   # agrl_graph_finalize[_bits]: a row's columns in four registers per lane
+PROPAGATE_TILED_MAX_V = 1024    # agrl_graph_propagate: 16 graph rows of V fp32 in 64 KB
+BACKWARD_RESIDENT_MAX_V = 116   # agrl_graph_matrix_backward: three V x V fp32 images + V floats in 160 KB (its message says 115; 116 fits and ran)
+PAIR_PRODUCT_MAX_V = 144        # agrl_graph_pair_product: two V x 128 fp32 slices in 160 KB
+
+
+def graph_forms(V, C):
+    """The kernel form each stage of a GraphLayer takes for V nodes of C channels (16-byte aligned tensors), mirrored from the
+    dispatch of the entry points -> dict stage -> name:
+      'gram'      'slices' (C / 128 partials, (B, C/128, V, V))          | 'tiled' (fully summed, (B, 1, V, V))
+      'finalize'  'resident' (a row in registers)                       | 'rows' (two passes over the row in HBM)
+      'propagate' 'stream' | 'mfma' | 'generic' | 'tiled'               | 'chunked' (16 graph rows through LDS in chunks)
+      'backward'  'resident' (three V x V images in LDS)                 | 'hbm' (three passes, M as scratch)
+      'pair'      'slices' (slice partials + their sum)                  | 'tiled' (no partials)
+    The left-hand names are the forms every V had to fit before; each stage switches at its own limit above."""
+    V, C = int(V), int(C)
+    assert V >= 1 and C >= 1
+    if V <= 64 and V % 4 == 0 and C % 128 == 0:
+        prop = "stream"
+    elif V <= 128 and C % 128 == 0:
+        prop = "mfma"
+    elif (V * ((V + 7) & ~7) + V * 128) * 4 <= 160 * 1024:
+        prop = "generic"
+    else:
+        prop = "tiled" if V <= PROPAGATE_TILED_MAX_V else "chunked"
+    return {"gram": "slices" if V <= GRAM_SLICE_MAX_V else "tiled",
+            "finalize": "resident" if V <= FINALIZE_RESIDENT_MAX_V else "rows",
+            "propagate": prop,
+            "backward": "resident" if V <= BACKWARD_RESIDENT_MAX_V else "hbm",
+            "pair": "slices" if V <= PAIR_PRODUCT_MAX_V else "tiled"}
+
+
+def _gram_into(f):
+    """The Gram of f (B,V,C) in the layout the consumers take, (B, nz, V, V): the C / 128 slice partials up to GRAM_SLICE_MAX_V
+    nodes, the fully summed tiled form (nz = 1) beyond. Called inside ``_dev(f)``."""
+    B, V, Cc = f.shape
+    nz = Cc // GRAM_CSLICE if graph_forms(V, Cc)["gram"] == "slices" else 1
+    gram = torch.empty((B, nz, V, V), dtype=torch.float32, device=f.device)
+    call("agrl_graph_gram", ptr(f), ptr(gram), B, V, Cc, GRAM_CSLICE, _stream(f))
+    return gram
+
 
 def graph_matrix(f, adj, use_pose, learn_graph, mask_diag=False):
     """f (B,V,C) fp32, adj (B,V,V) fp32 -> G (B,V,V). vmgn.py:114-120, :155-166; ``mask_diag``: ganet.py:259-268."""
@@ -1861,9 +1905,8 @@ def graph_matrix(f, adj, use_pose, learn_graph, mask_diag=False):
     nz = 0
     with _dev(f):
         if learn_graph:
-            nz = Cc // GRAM_CSLICE
-            gram = torch.empty((B, nz, V, V), dtype=torch.float32, device=f.device)
-            call("agrl_graph_gram", ptr(f), ptr(gram), B, V, Cc, GRAM_CSLICE, _stream(f))
+            gram = _gram_into(f.contiguous())
+            nz = gram.shape[1]
         if use_pose and adjacency_is_packed(adj):
             assert tuple(adj.shape) == (B, V, (V + 31) // 32)
             call("agrl_graph_finalize_bits", ptr(gram), nz, ptr(adj.contiguous()), ptr(G), B, V, 1, 1 if learn_graph else 0,
@@ -2719,25 +2762,22 @@ def attn_pool_backward(nodes, datt):
 
 
 def graph_gram(f):
-    """f (B,V,C) fp32 -> Gram partials (B, C/128, V, V) (first half of graph_matrix, kept for the backward pass)."""
-    B, V, Cc = f.shape
-    nz = Cc // GRAM_CSLICE
-    gram = torch.empty((B, nz, V, V), dtype=torch.float32, device=f.device)
+    """f (B,V,C) fp32 -> the Gram (B, nz, V, V) (first half of graph_matrix, kept for the backward pass): the C / 128 slice
+    partials up to GRAM_SLICE_MAX_V nodes, the fully summed tiled form (nz = 1) beyond."""
     with _dev(f):
-        call("agrl_graph_gram", ptr(f), ptr(gram), B, V, Cc, GRAM_CSLICE, _stream(f))
-    return gram
-
-
-PAIR_PRODUCT_MAX_V = 144
+        return _gram_into(f)
 
 
 def graph_pair_product(a, b):
-    """a, b (B,V,C) fp32 -> (B,V,V) with out[t] = a[t] b[t]^T (d loss / d G of the message pass, vmgn.py:168)."""
+    """a, b (B,V,C) fp32 -> (B,V,V) with out[t] = a[t] b[t]^T (d loss / d G of the message pass, vmgn.py:168); beyond
+    PAIR_PRODUCT_MAX_V nodes by the tiled kernel (no slice partials)."""
     B, V, Cc = a.shape
-    assert a.shape == b.shape and a.dtype == b.dtype == torch.float32 and Cc % GRAM_CSLICE == 0 and V <= PAIR_PRODUCT_MAX_V
-    part = torch.empty((B, Cc // GRAM_CSLICE, V, V), dtype=torch.float32, device=a.device)
+    assert a.shape == b.shape and a.dtype == b.dtype == torch.float32 and Cc % GRAM_CSLICE == 0
     out = torch.empty((B, V, V), dtype=torch.float32, device=a.device)
     with _dev(a):
+        part = None   # the slice partials, only where the slices form runs
+        if graph_forms(V, Cc)["pair"] == "slices":
+            part = torch.empty((B, Cc // GRAM_CSLICE, V, V), dtype=torch.float32, device=a.device)
         call("agrl_graph_pair_product", ptr(a.contiguous()), ptr(b.contiguous()), ptr(part), ptr(out), B, V, Cc, _stream(a))
     return out
 

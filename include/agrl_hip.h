@@ -426,7 +426,10 @@ int agrl_linear_nobias(const void* x, const void* w, float* y, int M, int K, int
  *   poses fp32 (B,S,18,3) AlphaPose keypoints (x, y, confidence); detected uint8 (B,S) -- 0 where the frame has no
  *   pose entry (its P x P blocks stay zero); height = frame height in pixels; threshold = 0.1 in the reference;
  *   num_split a power of two; pyramid_part != 0 adds the coarser stripe levels (P = 2 num_split - 1 nodes per frame).
- *   adj fp32 (B, S*P, S*P), values {0,1}, symmetric, zero diagonal: the layout GSTA.forward consumes (vmgn.py:292). */
+ *   adj fp32 (B, S*P, S*P), values {0,1}, symmetric, zero diagonal: the layout GSTA.forward consumes (vmgn.py:292).
+ *   1 <= S <= 5461 frames (the per-frame masks take 12 S bytes of the 64 KB of LDS a launch may ask for): whole tracklets of
+ *   --test-sample all (dataset_loader.py:115-120, max_len 1000) included. Up to S = 64 one workgroup builds a tracklet's graph,
+ *   beyond that up to 1024 share it. */
 int agrl_pose_adjacency(const float* poses, const unsigned char* detected, float* adj, int B, int S,
                         int num_split, int pyramid_part, float height, float threshold, agrl_stream_t stream);
 /* The same graph written bit-packed (layout: agrl_graph_finalize_bits), and the packing of an fp32 {0, 1} adjacency that
@@ -454,17 +457,24 @@ int agrl_part_pool(const void* x4_1, const void* x4_2, float* gsum, float* nodes
 
 /* Partial Gram matrices of the node features: gram_part[b][z][i][j] = sum over the z-th channel
  * slice of f[b,i,c]*f[b,j,c]. First half of GraphLayer.get_sim_matrix (dist_method='l2'),
- * torchreid/models/vmgn.py:114-118.  f fp32 (B,V,C); gram_part fp32 (B, nz, V, V); nz = C/cslice */
+ * torchreid/models/vmgn.py:114-118.  f fp32 (B,V,C); gram_part fp32 (B, nz, V, V); nz = C/cslice
+ * Any V >= 1; cslice must be 128 and divide C. Up to V = 304 a V x 128 slice sits in LDS and nz = C / 128 partials are written.
+ * Beyond, the (B, C/128, V, V) partials would be 3 GB per tracklet at V = 7000: the Gram is computed in 64 x 64 tiles by
+ * v_mfma_f32_16x16x4_f32 with one fp32 accumulator per element over ALL channels in a fixed order and written fully summed,
+ * gram_part fp32 (B, 1, V, V) -- the consumers below take it with nz = 1. Only the tiles i <= j are computed and
+ * mirror-stored: the result is bit-symmetric and g_ii exists once, so D2_ii = (n_i + n_i) - 2 g_ii stays exactly 0. */
 int agrl_graph_gram(const float* f, float* gram_part, int B, int V, int C, int cslice,
                     agrl_stream_t stream);
-
 /* Finish the adaptive graph: sum the Gram partials, d = sqrt(clamp(n_i+n_j-2g_ij, 1e-12)),
  * sim = 2/(exp(d)+1), row-L1-normalise sim and adj, G = (adj^ + sim^)/2 (or one of them).
  * torchreid/models/vmgn.py:118-120 and :155-166.
  *   adj fp32 (B,V,V) or NULL when use_pose == 0; gram_part may be NULL when learn_graph == 0
  *   mask_diag != 0: the sibling model ganet's form -- self-loops (the diagonal of adj and of sim) are zeroed before the row-L1
  *   normalisation, torchreid/models/ganet.py:259-268
- *   G   fp32 (B,V,V) */
+ *   G   fp32 (B,V,V)
+ *   Any V: up to V = 256 a row's columns stay in registers; beyond, rows are streamed from HBM in two passes (row sum, then
+ *   write) with the same arithmetic and the same row-sum shape. gram_part is (B, nz, V, V) either way: nz = C / 128 partials of
+ *   agrl_graph_gram up to V = 304, its fully summed nz = 1 result beyond. */
 int agrl_graph_finalize(const float* gram_part, int nz, const float* adj, float* G, int B, int V,
                         int use_pose, int learn_graph, int mask_diag, agrl_stream_t stream);
 /* agrl_graph_finalize with the pose adjacency in the bit-packed form of agrl_pose_adjacency_bits / agrl_adjacency_pack:
@@ -503,7 +513,9 @@ int agrl_graph_linear_mix(const void* p_op, const void* w, const float* f, const
  * torchreid/models/vmgn.py:168-172 with keep = (float)(1.0 - gamma) (the reference's Python-float 1 - gamma, rounded once);
  * torchreid/models/ganet.py:278-283 with keep = 1 (``input + gamma * h'``).
  *   f,h fp32 (B,V,C); G fp32 (B,V,V); out fp32 (B,V,C); out_lp NULL or bf16 copy of out (the A
- *   operand of the next layer's bf16 Linear). Deterministic: no atomics. */
+ *   operand of the next layer's bf16 Linear). Deterministic: no atomics. Any V: V <= 64 streaming, V <= 128 MFMA, graph and h
+ *   slab in LDS while they fit 160 KB, 16 graph rows per workgroup up to V = 1024, and beyond that the same 16 rows staged
+ *   through LDS in chunks of 512 columns (one running accumulator per output, u ascending: the order of the V <= 1024 form). */
 int agrl_graph_propagate(const float* f, const float* h, const float* G, const float* bn_scale,
                          const float* bn_shift, float keep, float gamma, float slope, float* out, void* out_lp,
                          int B, int V, int C, agrl_stream_t stream);
@@ -843,14 +855,18 @@ int agrl_attn_pool_backward(const float* nodes, const float* datt, float* dnodes
 /* Backward of the adaptive graph (agrl_graph_gram + agrl_graph_finalize; vmgn.py:114-120, :155-166) w.r.t. the node
  * features: from the forward's Gram partials and dG fp32 (B,V,V) -> M fp32 (B,V,V) with d loss / d f[b] = M[b] f[b] (apply it
  * with agrl_graph_propagate: keep 0, gamma 1, unit scale, zero shift, slope 1). The diagonal D2_ii == 0 passes no gradient
- * (exact arithmetic; the reference's autograd forms it as two cancelling fp32 terms). V <= 115. */
+ * (exact arithmetic; the reference's autograd forms it as two cancelling fp32 terms). Any V; gram_part (B, nz, V, V) with
+ * nz >= 1, whichever layout agrl_graph_gram produced. Up to V = 116 three V x V images sit in LDS; beyond, the same formulas,
+ * conventions and reduction shape run as three passes over the V x V image in HBM, with M itself as the only scratch. */
 int agrl_graph_matrix_backward(const float* gram_part, int nz, const float* dG, float* M, int B, int V, int use_pose,
                                int mask_diag, agrl_stream_t stream);
 
 /* Per-tracklet product out[b] = a[b] b[b]^T of two node matrices, fp32 (B,V,C) each -> fp32 (B,V,V): the gradient of the
  * message pass msg = G h (vmgn.py:168) w.r.t. the graph, d loss / d G[b] = dmsg[b] h[b]^T. Exact fp32 MFMA over 128-channel
  * slices (the agrl_graph_gram kernel with two operands), slice partials summed in slice order. part: workspace of
- * B * (C/128) * V * V floats. C % 128 == 0, V <= 144 (two V x 128 fp32 slices in LDS). */
+ * B * (C/128) * V * V floats. C % 128 == 0; any V. Up to V = 144 two V x 128 fp32 slices sit in LDS; beyond, the two-operand
+ * form of the tiled Gram kernel (all V x V tiles, no mirror, one fp32 accumulator per element over all C channels) writes out
+ * directly and part is not used (it may be NULL). */
 int agrl_graph_pair_product(const float* a, const float* b, float* part, float* out, int B, int V, int C, agrl_stream_t stream);
 
 /* CrossEntropyLabelSmooth (torchreid/losses/cross_entropy_loss.py:26-37), value and gradient in one call:
